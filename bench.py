@@ -2,7 +2,7 @@
 """
 bench.py -- BASELINE.json metric: GCN-layer fwd+bwd sentences/sec at batch=50 seq=100 h=200 on N MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1: launched by torch.distributed.run, or self-launched)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run, or self-launched)
 
 One "step" = the hot path over one synthetic TACRED-shaped batch of 50 sentences x 100 tokens
 (BASELINE.json configs[1]: 2-layer GCN, no LSTM, Din 360 -> 200 -> 200, prune_k 1, bf16 storage,
@@ -93,6 +93,10 @@ def parse():
                     "with_cached_trees steps instead of a side job of the tree launch")
     ap.add_argument("--no-pooled-only", action="store_true", help="skip the secondary pooled-only-rows measurement (profiling runs: its launches "
                                                                   "would mix into the per-kernel statistics of the headline step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0: layer outputs, input gradients, the gradient bucket "
+                         "and, for N > 1, the updated weights) as DIR/<name>.npy in float32, at most 64 MB in all; the inputs are seeded, so "
+                         "two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
 
 
@@ -192,6 +196,16 @@ class Stack(object):
         f = self.buckets[k]
         o = [0, H * Din, H * Din + H, H * Din + H + H * H]
         return f[o[0]:o[1]], f[o[1]:o[2]], f[o[2]:o[3]], f[o[3]:]
+
+    def outputs(self, k=0, with_weights=False):
+        """What a caller of the step receives (--dump-outputs): both layers' outputs [rows, H], the input gradient dx [rows, Din] and
+        gradient bucket k as [dW0, db0, dW1, db1]; with_weights: the parameters too (N > 1: the SGD updates changed them).  Not dh1:
+        the backward sweep leaves layer 0's dZ there (include/gcnpt.h, gcnpt_layers_bwd), caller scratch rather than a result."""
+        dW0, db0, dW1, db1 = self.grads(k)
+        out = dict(h1=self.h1, h2=self.h2, dx=self.dx, dW0=dW0.view(self.H, self.Din), db0=db0, dW1=dW1.view(self.H, self.H), db1=db1)
+        if with_weights:
+            out.update(W0=self.W[0], b0=self.b[0], W1=self.W[1], b1=self.b[1])
+        return out
 
     # ---- tree launches (each only enqueues on the current stream) ----
     def prune(self, pack=False):
@@ -444,6 +458,26 @@ def timed(run, steps, warmup, barrier):
     barrier()
     wall = time.perf_counter() - t0
     return wall, e0.elapsed_time(e1) * 1e-3
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: cap on all files together
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_BYTES, seed=0):
+    """Writes every tensor of `arrays` (name -> tensor) as path/<name>.npy in float32 (bf16 widens exactly).  When they would exceed
+    max_bytes together, every 2-D array keeps the same fraction of its rows, drawn with a fixed seed from its row count alone (so arrays
+    with equal row counts keep the same rows, and two runs keep the same rows); 1-D arrays are always kept whole."""
+    os.makedirs(path, exist_ok=True)
+    b2 = sum(4 * a.numel() for a in arrays.values() if a.dim() == 2)
+    b1 = sum(4 * a.numel() for a in arrays.values() if a.dim() != 2) + 4096 * len(arrays)      # + room for each file's .npy header
+    frac = 1.0 if b1 + b2 <= max_bytes else max(0.0, max_bytes - b1) / b2
+    for name, a in arrays.items():
+        a = a.detach()
+        if frac < 1.0 and a.dim() == 2:
+            n = a.shape[0]
+            keep = np.sort(np.random.default_rng(seed).choice(n, max(1, int(n * frac)), replace=False))
+            a = a.index_select(0, torch.from_numpy(keep).to(a.device))
+        np.save(os.path.join(path, name + ".npy"), a.float().cpu().numpy())
 
 
 def kernel_breakdown(stack, use_graph, rounds=100, reps=8):
@@ -799,6 +833,10 @@ def main():
     stack.wflat.copy_(w0)
     wall, ev = timed(make_run(replays, exchange, reducer), args.steps, args.warmup, barrier)
     drain()
+    last_k = (args.steps - 1) % N_BUCKETS if (multi and exchange == "async") else 0     # the bucket the LAST timed step wrote
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on these buffers: the repeats and secondary legs below overwrite them (and, N > 1, reset W)
+        dump_outputs(args.dump_outputs, stack.outputs(last_k, with_weights=multi))
     # the contract's `value` / `ms_per_step` are that ONE K-step region; beside it the median over repeats of the same region (a
     # 20-step region is ~1 ms: one sample is at the mercy of whatever else the host does in that millisecond)
     reps_ms = []
@@ -816,7 +854,7 @@ def main():
         wall = max(float(t.item()) for t in every)                 # contract: MAX over ranks
     assert torch.isfinite(stack.buckets[0]).all() and torch.isfinite(stack.dx.float()).all() and torch.isfinite(stack.wflat).all()
     # the bucket the LAST timed step wrote, after its all-reduce: rank-sum of [dW0, db0, dW1, db1]
-    last_bucket = stack.buckets[(args.steps - 1) % N_BUCKETS if (multi and exchange == "async") else 0]
+    last_bucket = stack.buckets[last_k]
     grad_abs_sum = float(last_bucket.double().abs().sum().item())
     weight_drift = float((stack.wflat - w0).double().abs().sum().item())      # > 0 iff the SGD updates were applied (N > 1, sync)
 

@@ -1,7 +1,8 @@
 """
 bench.py as the driver invokes it: `python bench.py --gpus N` must start N ranks itself (the reference has no
 distributed entry point at all, train_cgcn.sh:5 picks one GPU).  CPU tests cover the refusals that need no GPU; the `gpu` test
-runs the real self-launch with two ranks sharing the one GPU of the box over gloo (GCNPT_BENCH_ONE_DEVICE=1).
+runs the real self-launch with two ranks sharing the one GPU of the box over gloo (GCNPT_BENCH_ONE_DEVICE=1).  --dump-outputs: its size
+cap and row sample on the CPU, its arrays against the CPU oracle on the GPU.
 """
 import json
 import os
@@ -64,3 +65,62 @@ def test_self_launch_two_ranks_one_device():
     assert d2["config"]["dp_mode"].startswith("synchronous SGD") and d2["config"]["weight_abs_drift_after_timed_steps"] > 0
     assert "async_upper_bound" in d2 and "NOT synchronous" in d2["async_upper_bound"]["note"]
     assert d1["config"]["dp_mode"] == "none (1 GPU)"
+
+
+def test_dump_outputs_stays_under_cap_with_a_fixed_sample(tmp_path):
+    """--dump-outputs writes float32 .npy files, at most 64 MB in all: above that, every 2-D array keeps the same seeded rows (the same
+    ones in every run, and in every array with that row count); 1-D arrays stay whole."""
+    import numpy as np
+    import torch
+
+    import bench
+    n = 40000
+    h = torch.randn(n, 300)
+    dx = torch.randn(n, 600)
+    dx[:, 0] = torch.arange(n, dtype=torch.float32)                    # row ids, to find which rows were kept
+    arrays = {"h": h.to(torch.bfloat16), "dx": dx, "db": torch.randn(300)}
+    assert 4 * sum(a.numel() for a in arrays.values()) > bench.DUMP_BYTES
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_BYTES
+        got.append({f.stem: np.load(f) for f in (tmp_path / d).iterdir()})
+    a, b = got
+    assert sorted(a) == ["db", "dx", "h"] and all(v.dtype == np.float32 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["db"], arrays["db"].numpy())
+    rows = a["dx"][:, 0].astype(np.int64)
+    assert 0 < len(rows) < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["dx"], dx.numpy()[rows]) and np.array_equal(a["h"], arrays["h"].float().numpy()[rows])
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_timed_step_computed(tmp_path):
+    """--dump-outputs at fp32 without dropout: the arrays of the last timed step match the CPU oracle on the same seeded inputs
+    (rank 0's shard seed 1234), whatever the number of steps and the launch mode."""
+    import numpy as np
+
+    from gcn_over_pruned_trees_amd.utils import synthetic
+    from helpers import FWD_RTOL, GRAD_RTOL, max_rel
+    from oracle import gcn_ref, prune_ref
+    B, T, Din, H = 4, 20, 200, 200
+    tb = synthetic.random_tree_batch(1234, B, T, "full")
+    Ws, bs = synthetic.layer_params(1235, [Din, H, H])
+    x, gy = synthetic.normal(1236, (B, T, Din)), synthetic.normal(1237, (B, T, H))
+    adj = prune_ref.batch_adj(tb["head"], tb["subj_pos"], tb["obj_pos"], tb["deprel"], tb["lens"], 1)["adj"]
+    h1, _ = gcn_ref.gcn_forward(adj, x, Ws[:1], bs[:1])
+    h2, _ = gcn_ref.gcn_forward(adj, x, Ws, bs)
+    dx, dWs, dbs = gcn_ref.gcn_backward(adj, x, Ws, bs, gy)
+    want = dict(h1=h1, h2=h2, dx=dx, dW0=dWs[0], db0=dbs[0], dW1=dWs[1], db1=dbs[1])
+    shape = ["--batch", str(B), "--seq", str(T), "--din", str(Din), "--hidden", str(H), "--dtype", "fp32", "--drop", "0", "--repeats", "1"]
+    for steps, launch in (("3", "native"), ("7", "graph")):
+        out = tmp_path / launch
+        r = _run(["--gpus", "1", "--steps", steps, "--warmup", "1", "--launch", launch, "--dump-outputs", str(out)] + shape + FAST)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = {f.stem: np.load(f) for f in out.iterdir()}
+        assert sorted(got) == sorted(want) and all(v.dtype == np.float32 for v in got.values())
+        for k, v in want.items():
+            v = v.reshape(-1, v.shape[-1]) if v.ndim == 3 else v                # [B, T, *] activations are dumped as [rows, *]
+            assert got[k].shape == v.shape, (k, got[k].shape, v.shape)
+            err = max_rel(got[k], v)
+            assert err <= (FWD_RTOL if k in ("h1", "h2") else GRAD_RTOL), (launch, k, err)
