@@ -81,6 +81,8 @@ SIGNATURES = {
     "gcnpt_bilinear_de_planes": (_i, [_i, _i, _i, _i, _i]),
     "gcnpt_bilinear_bwd_e": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _i]),
     "gcnpt_bilinear_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _i]),
+    "gcnpt_lstm_fwd": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "gcnpt_lstm_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p]),
 }
 
 

@@ -12,8 +12,8 @@ signatures as the reference, so `from model.gcn import GCNClassifier` can be swa
 
 What is different underneath: the tree pruning + adjacency build (gcn.py:96-110) is one device kernel
 (model/tree.py here) and every iteration of the layer loop (gcn.py:266-393) is one fused HIP kernel per
-direction, reached through the C-ABI of include/gcnpt.h.  Embeddings, the optional BiLSTM, pooling and
-the output MLP stay ordinary PyTorch-ROCm modules, as in the reference.
+direction, reached through the C-ABI of include/gcnpt.h.  Embeddings, pooling and the output MLP stay ordinary
+PyTorch-ROCm modules, as in the reference; so does the optional BiLSTM unless opt['gcn_native_rnn'] is set.
 
 New optional `opt` keys (defaults reproduce the reference): `gcn_dtype` = 'fp32' | 'bf16' (MFMA operand /
 activation storage type inside the layer stack), `gcn_check_trees` = True (synchronise once per forward to
@@ -23,8 +23,10 @@ layer loop runs on token-packed rows, sum(len) instead of B*T, padding only at t
 hands the top layer its dZ), `gcn_pack_with_trees` = True (the tree launch also packs the weights in a training step),
 `gcn_sparse_emb_grad` = False (True: the word-embedding table's gradient is a row-sparse tensor of the batch's token rows, for
 shard.SparseRowExchange in a data-parallel loop), `gcn_reuse_packed_weights` = False (True: a forward may reuse the packed weight images of the previous one while the weights'
-version counters stand still -- gradient accumulation, a frozen model; off by default because `p.data` updates do not bump them, in eval() either) -- with `gcn_check_trees=False` a whole training step of the no-LSTM
-model can be captured with torch.cuda.graph and replayed, see tests/test_gpu_parity.py::test_training_step_graph_capture).
+version counters stand still -- gradient accumulation, a frozen model; off by default because `p.data` updates do not bump them, in eval() either),
+`gcn_native_rnn` = False (True: the C-GCN model's BiLSTM runs on the native recurrence of model/rnn.py with the lengths on the device, output
+[B, T, 2H]) -- with `gcn_check_trees=False` a whole training step can be captured with torch.cuda.graph and replayed: the no-LSTM model as
+it is (tests/test_gpu_parity.py::test_training_step_graph_capture), the C-GCN model with `gcn_native_rnn=True` (tests/test_gpu_lstm.py).
 """
 import ctypes
 
@@ -34,6 +36,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..utils import constant
+from .rnn import bilstm
 from .tree import CompactTrees, PackedTrees, PrunedTrees, adj_to_csr, prune_to_csr, prune_to_csr_packed
 
 
@@ -567,6 +570,9 @@ class GCN(nn.Module):
         return embs * torch.gather(keep, 1, words).unsqueeze(-1) / (1 - p)
 
     def encode_with_rnn(self, rnn_inputs, masks, batch_size):
+        if self.opt.get('gcn_native_rnn', False):
+            # the native recurrence (model/rnn.py): lengths stay on the device, the output is [B, T, 2H] (zeros past each sentence)
+            return bilstm(rnn_inputs.float(), masks.eq(0).sum(1).int(), self.rnn, self.training)
         lens = masks.eq(0).long().sum(1).cpu()
         shape = (self.opt['rnn_layers'] * 2, batch_size, self.opt['rnn_hidden'])
         h0 = rnn_inputs.new_zeros(shape)

@@ -97,6 +97,29 @@ int gcnpt_get_option(int option);
 int gcnpt_sgd_clip_update(void* stream, float* w, const float* g, long long n, float g_scale, float max_norm, float lr, float* partials,
                           const float* extra_sq);
 
+/* ---- the C-GCN model's BiLSTM recurrence (reference model/gcn.py:186-197 GCN.encode_with_rnn + 485-492 rnn_zero_state: nn.LSTM(
+ * bidirectional=True, batch_first=True) over pack_padded_sequence(x, lens, enforce_sorted=False) from a zero state, then pad_packed_sequence) ---
+ * Only the step-to-step recurrence of ONE layer, both directions, exact fp32 (v_mfma_f32_16x16x4_f32); the time-parallel products
+ * (Gx = x W_ih^T + b_ih + b_hh, dx, dW_ih, dW_hh, db) are the caller's GEMMs (model/rnn.py).  Each call enqueues T launches, one per step s,
+ * and nothing else: no allocation, no host sync, so a whole C-GCN training step captures into a hipGraph.  Gate order i, f, g, o; h0 = c0 = 0.
+ * lens [dev] int32 [B], clamped to [0, T] by the kernels (the lengths never visit the host).  Sentence b: the forward direction runs
+ * t = 0 .. len-1, the reverse direction t = len-1 .. 0; rows t >= len of every output are 0.  A length of 0 gives an all-zero sentence
+ * (pack_padded_sequence raises on it).  w_hh_f / w_hh_r [dev] float32 [4H,H] as nn.LSTM holds weight_hh_l{k} / weight_hh_l{k}_reverse.
+ * Rows r = b*T + t; column of direction d, gate g, unit u: d*4H + g*H + u in the [B*T, 8H] tensors, d*H + u in the [B*T, 2H] tensors.
+ * gcnpt_lstm_fwd: gx [dev] [B*T, gx_cols = 8H] (both directions' Gx); writes y [B*T,2H] (the layer output), c [B*T,2H] (the cell state,
+ *   always needed); for a backward pass also gates [B*T,8H] (the activated i, f, g, o) and h_prev [B*T,2H] (the h each step started from, 0
+ *   at a sentence's first step and on padding: dW_hh = sum_t dG_t^T h_prev_t as one GEMM per direction), else NULL.
+ * gcnpt_lstm_bwd: dy [dev] [B*T,2H], c and gates from the forward; writes dgates [B*T,8H] (the gradient of the gate pre-activations, 0 on
+ *   padding rows) completely; dc [dev] float32 [2*B*H] is scratch (no initialisation needed).
+ * Checks without a GPU: null pointers and B, T, H < 1 -> GCNPT_E_INVALID, a gate width other than 8H -> GCNPT_E_INVALID,
+ * B*T*8H beyond 32-bit indexing -> GCNPT_E_UNSUPPORTED. */
+/* replaces model/gcn.py:194-196 forward (pack, self.rnn, pad) with h0 = c0 = 0 (rnn_zero_state, gcn.py:485-492) */
+int gcnpt_lstm_fwd(void* stream, const float* gx, int gx_cols, const float* w_hh_f, const float* w_hh_r, const int32_t* lens, int B, int T,
+                   int H, float* y, float* c, float* gates, float* h_prev);
+/* replaces the autograd backward of model/gcn.py:194-196 through the LSTM's recurrence (cuDNN/MIOpen RNN backward-data) */
+int gcnpt_lstm_bwd(void* stream, const float* dy, const float* w_hh_f, const float* w_hh_r, const int32_t* lens, int B, int T, int H,
+                   const float* c, const float* gates, int gates_cols, float* dgates, float* dc);
+
 /* ---- measurement aids (no reference counterpart) --------------------------------------------------------------
  * gcnpt_last_launch: grid, workgroup size, dynamic LDS bytes and kernel-argument bytes of the calling thread's most recent launch of
  * the layer path (pack, layer forward / backward-data, weight gradient).  gcnpt_launch_empty: enqueues a kernel of that shape whose

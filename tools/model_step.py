@@ -4,7 +4,8 @@ Full-model step times through the drop-in modules ("plus full-mode
 device copy bandwidth (the denominator SURVEY asks for beside the nominal 8 TB/s).  Synthetic TACRED-shaped batch, random
 weights; eager launches (ctypes + torch), one optimizer-free fwd+bwd per step.  Prints one JSON object.
   C2: GCNClassifier, 2-layer GCN, no LSTM, B=50 T=100 hidden=200 (emb 300 + pos 30 + ner 30)
-  C3: the same with the BiLSTM in front (rnn_hidden 200), i.e. C-GCN
+  C3: the same with the BiLSTM in front (rnn_hidden 200), i.e. C-GCN; C3_cgcn_native_rnn: its BiLSTM on the native recurrence
+      (opt['gcn_native_rnn'], model/rnn.py) instead of MIOpen's
 """
 import json
 import os
@@ -19,11 +20,11 @@ from gcn_over_pruned_trees_amd.model import gcn, tree  # noqa: E402
 from gcn_over_pruned_trees_amd.utils import synthetic  # noqa: E402
 
 
-def opt_for(rnn, dtype):
+def opt_for(rnn, dtype, native_rnn=False):
     return dict(vocab_size=5000, emb_dim=300, pos_dim=30, ner_dim=30, hidden_dim=200, num_layers=2, input_dropout=0.5, gcn_dropout=0.5,
                 word_dropout=0.04, emb_dropout=0.0, topn=1e10, prune_k=1, pooling="max", pooling_l2=0.003, mlp_layers=2, no_adj=False,
                 rnn=rnn, rnn_hidden=200, rnn_layers=1, rnn_dropout=0.5, cuda=True, dataset="tacred", num_class=42, adj_type="regular",
-                gcn_dtype=dtype, gcn_check_trees=False)
+                gcn_dtype=dtype, gcn_check_trees=False, gcn_native_rnn=native_rnn)
 
 
 def main():
@@ -38,10 +39,10 @@ def main():
               t(tb["deprel"]), t(tb["head"]), t(tb["subj_pos"]), t(tb["obj_pos"]))
     labels = t(rng.randint(0, 42, size=(B,)).astype(np.int64))
     out = {}
-    for name, rnn in (("C2_gcn", False), ("C3_cgcn", True)):
+    for name, rnn, native in (("C2_gcn", False, False), ("C3_cgcn", True, False), ("C3_cgcn_native_rnn", True, True)):
         for dtype in ("fp32", "bf16"):
             torch.manual_seed(1234)
-            model = gcn.GCNClassifier(opt_for(rnn, dtype)).to(dev).train()
+            model = gcn.GCNClassifier(opt_for(rnn, dtype, native)).to(dev).train()
             cache = tree.TreeCache.build(inputs[5], inputs[6], inputs[7], inputs[4], 1, masks=inputs[1], want_label=False)
             idx = torch.arange(B, device=dev)
 
@@ -76,7 +77,7 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     out["copy_bandwidth_GBps"] = round(20 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-    out["note"] = "eager launches through the modules (no hipGraph): embeddings, optional BiLSTM (MIOpen), pruner or cached trees, GCN layers, " \
+    out["note"] = "eager launches through the modules (no hipGraph): embeddings, optional BiLSTM (MIOpen, or the native recurrence in C3_cgcn_native_rnn), pruner or cached trees, GCN layers, " \
                   "fused pooling, MLP, loss, backward; B=50 T=100"
     print(json.dumps(out))
 

@@ -5,6 +5,8 @@ backward) on the tokens of the pruned trees only (CompactTrees) an
 ONE hipGraph.
 The mirror looks embeddings up through its own autograd function (index_add_ backward): PyTorch-ROCm 2.10's embedding backward
 takes ~140 us per table and, above 3072 indices, a rocPRIM sort path that cannot be replayed in a hipGraph.
+C3_cgcn_native_rnn_*: the same for the C-GCN model (BiLSTM 200 in front) with opt['gcn_native_rnn'], the only form of its step that
+can be captured.
 Prints one JSON object.
 """
 import json
@@ -25,7 +27,8 @@ def main():
     dev = torch.device("cuda:0")
     B, T = 50, 100
     out = {}
-    for lengths, compact in (("tacred", True), ("full", True), ("tacred", False)):
+    for rnn, lengths, compact in ((False, "tacred", True), (False, "full", True), (False, "tacred", False), (True, "tacred", True),
+                                  (True, "tacred", False)):
         tb = synthetic.random_tree_batch(1236, B, T, lengths)
         rng = np.random.RandomState(7)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -35,7 +38,7 @@ def main():
                   t(tb["deprel"]), t(tb["head"]), t(tb["subj_pos"]), t(tb["obj_pos"]))
         labels = t(rng.randint(0, 42, size=(B,)).astype(np.int64))
         torch.manual_seed(1234)
-        opt = dict(opt_for(False, "bf16"), gcn_graph_rng=True, word_dropout=0.0)
+        opt = dict(opt_for(rnn, "bf16", native_rnn=rnn), gcn_graph_rng=True, word_dropout=0.0)
         model = gcn.GCNClassifier(opt).to(dev).train()
         cache = tree.TreeCache.build(inputs[5], inputs[6], inputs[7], inputs[4], 1, masks=inputs[1], want_label=False, compact=True)
         idx = torch.arange(B, device=dev)
@@ -58,7 +61,7 @@ def main():
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n
 
-        key = "C2_gcn_bf16_%s_%s_len" % ("pooled_only" if compact else "all_rows", lengths)
+        key = "%s_bf16_%s_%s_len" % ("C3_cgcn_native_rnn" if rnn else "C2_gcn", "pooled_only" if compact else "all_rows", lengths)
         dt = timeit(step)
         out[key] = dict(rows=B * Tc, rows_full=B * T, eager_ms_per_step=round(dt * 1e3, 3), eager_sentences_per_s=round(B / dt))
         if True:        # (the mirror's own embedding backward, model/gcn.py::_EmbedFn, has no index-count limit)
@@ -76,7 +79,7 @@ def main():
             dt = timeit(graph.replay)
             out[key].update(hipgraph_ms_per_step=round(dt * 1e3, 3), hipgraph_sentences_per_s=round(B / dt), loss=float(loss))
         del model
-    out["note"] = "GCNClassifier fwd+bwd (no optimizer), B=50 T=100, bf16 layer stack, CompactTrees from a TreeCache; eager = ctypes + torch " \
+    out["note"] = "GCNClassifier fwd+bwd (no optimizer), B=50 T=100, bf16 layer stack (C3: fp32 BiLSTM 200 on the native recurrence), CompactTrees from a TreeCache; eager = ctypes + torch " \
                   "launches from Python, hipgraph = the same step captured once with torch.cuda.graph and replayed"
     print(json.dumps(out))
 
