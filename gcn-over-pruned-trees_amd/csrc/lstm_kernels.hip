@@ -8,7 +8,7 @@
 // issues all its operand loads at once (one round trip for H <= 256) and the element-wise operands are requested before the contraction.  Sentence b with length len:
 //   forward direction  works at t = s            for s < len
 //   reverse direction  works at t = len - 1 - s  for s < len   (it starts at the sentence's own end, not at T - 1)
-//   s >= len           both directions write the padding row t = s: y = 0, h_prev = 0, dG = 0
+//   s >= len           both directions write the padding row t = s: y = c = h_prev = gates = 0 forward, dG = 0 backward
 // so every row of every output is written exactly once per call and no buffer needs clearing.
 //
 // Layouts (rows r = b*T + t): gx / gates / dgates float32 [B*T, 8H] with column d*4H + g*H + u (gate order i, f, g, o: nn.LSTM's);
@@ -99,6 +99,11 @@ __global__ __launch_bounds__(LSTM_THREADS) void lstm_fwd_step_kernel(const float
         const size_t oz = (size_t)(b * T + s) * H2 + d * H + u;
         y[oz] = 0.f;
         c[oz] = 0.f;
+        if (gates) {
+            const size_t rz = (size_t)(b * T + s) * G8 + d * 4 * H + u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) gates[rz + g * H] = 0.f;
+        }
         if (h_prev) h_prev[oz] = 0.f;
         return;
     }

@@ -107,10 +107,12 @@ int gcnpt_sgd_clip_update(void* stream, float* w, const float* g, long long n, f
  * (pack_padded_sequence raises on it).  w_hh_f / w_hh_r [dev] float32 [4H,H] as nn.LSTM holds weight_hh_l{k} / weight_hh_l{k}_reverse.
  * Rows r = b*T + t; column of direction d, gate g, unit u: d*4H + g*H + u in the [B*T, 8H] tensors, d*H + u in the [B*T, 2H] tensors.
  * gcnpt_lstm_fwd: gx [dev] [B*T, gx_cols = 8H] (both directions' Gx); writes y [B*T,2H] (the layer output), c [B*T,2H] (the cell state,
- *   always needed); for a backward pass also gates [B*T,8H] (the activated i, f, g, o) and h_prev [B*T,2H] (the h each step started from, 0
- *   at a sentence's first step and on padding: dW_hh = sum_t dG_t^T h_prev_t as one GEMM per direction), else NULL.
+ *   always needed); for a backward pass also gates [B*T,8H] (the activated i, f, g, o; 0 on padding rows) and h_prev [B*T,2H] (the h
+ *   each step started from, 0 at a sentence's first step and on padding: dW_hh = sum_t dG_t^T h_prev_t as one GEMM per direction), else
+ *   NULL.  Every row of each output it writes is written, padding included: no buffer needs clearing.
  * gcnpt_lstm_bwd: dy [dev] [B*T,2H], c and gates from the forward; writes dgates [B*T,8H] (the gradient of the gate pre-activations, 0 on
- *   padding rows) completely; dc [dev] float32 [2*B*H] is scratch (no initialisation needed).
+ *   padding rows) completely; dc [dev] float32 [2*B*H] needs no initialisation and afterwards holds, as [2, B, H], dL/dc of each
+ *   direction's zero initial cell state (0 for a sentence of length 0).
  * Checks without a GPU: null pointers and B, T, H < 1 -> GCNPT_E_INVALID, a gate width other than 8H -> GCNPT_E_INVALID,
  * B*T*8H beyond 32-bit indexing -> GCNPT_E_UNSUPPORTED. */
 /* replaces model/gcn.py:194-196 forward (pack, self.rnn, pad) with h0 = c0 = 0 (rnn_zero_state, gcn.py:485-492) */
