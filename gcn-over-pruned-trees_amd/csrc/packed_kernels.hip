@@ -148,9 +148,9 @@ extern "C" int gcnpt_pack_trees(void* stream, const int32_t* src_row_ptr, const 
     GCNPT_REQUIRE(src_row_ptr && src_col_idx && src_ell && src_pool_mask && len, "pack_trees: null source pointer");
     GCNPT_REQUIRE(cu_seqlens && row_ptr && col_idx && ell && pool_mask && row_sent && status, "pack_trees: null destination pointer");
     GCNPT_REQUIRE(B > 0 && T > 0 && cap > 0 && n_rows > 0 && nnz_cap > 0, "pack_trees: sizes must be positive");
-    GCNPT_REQUIRE(!label || src_label, "pack_trees: labels wanted but the source has none");
-    GCNPT_REQUIRE((!rowT_ptr && !colT_idx && !ellT) || (rowT_ptr && colT_idx && ellT && src_rowT_ptr && src_colT_idx && src_ellT),
-                  "pack_trees: the transposed pattern is all-or-nothing");
+    const int rc = check_request("pack_trees", src_label, src_rowT_ptr, src_colT_idx, src_ellT, src_pool_mask, label, rowT_ptr, colT_idx, ellT,
+                                 pool_mask);
+    if (rc != GCNPT_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     GCNPT_HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), s));
     PackSrc a{src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask, len};

@@ -1054,16 +1054,58 @@ __global__ __launch_bounds__(COMPACT_THREADS) void compact_trees_kernel(const Tr
             dst.colT_idx[(size_t)b * cap_c + k] = c_slot[min(max(src.colT_idx[(size_t)b * cap + k], 0), T - 1)];
 }
 
+// what a rewrite of a batch's arrays (gather / pack / compact) may ask of its source: labels, the transposed pattern (all or nothing) and
+// the pool mask only where the source holds them; what: the entry point, for the messages
+int check_request(const char* what, const int32_t* src_label, const int32_t* src_rowT_ptr, const int32_t* src_colT_idx,
+                  const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* label, const int32_t* rowT_ptr,
+                  const int32_t* colT_idx, const int32_t* ellT, const uint8_t* pool_mask) {
+    GCNPT_REQUIRE(!label || src_label, "%s: labels wanted but the source holds none", what);
+    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr) && (rowT_ptr == nullptr) == (ellT == nullptr),
+                  "%s: rowT_ptr, colT_idx and ellT go together", what);
+    GCNPT_REQUIRE(!rowT_ptr || (src_rowT_ptr && src_colT_idx && src_ellT), "%s: transposed pattern wanted but the source holds none", what);
+    GCNPT_REQUIRE(!pool_mask || src_pool_mask, "%s: pool mask wanted but the source holds none", what);
+    return GCNPT_OK;
+}
+
 }  // namespace gcnpt
 
 using namespace gcnpt;
 
-// pack_blocks > 0: that many extra workgroups of the launch pack the weights described by pk (side job)
+// the source arrays of a gather / compact launch as the kernel takes them (read only); the transposed pattern only when it is wanted
+static TreeArrays source_arrays(const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label, const int32_t* rowT_ptr,
+                                const int32_t* colT_idx, const int32_t* ell, const int32_t* ellT, const uint8_t* pool_mask,
+                                const int32_t* status, bool want_transpose) {
+    return TreeArrays{const_cast<int32_t*>(row_ptr), const_cast<int32_t*>(col_idx), const_cast<int32_t*>(label),
+                      const_cast<int32_t*>(want_transpose ? rowT_ptr : nullptr), const_cast<int32_t*>(colT_idx), const_cast<int32_t*>(ell),
+                      const_cast<int32_t*>(ellT), const_cast<uint8_t*>(pool_mask), const_cast<int32_t*>(status)};
+}
+
+// the weight pack a tree launch may carry as a side job: `blocks` extra workgroups of the launch pack the images described by pk
+struct SideJob {
+    PackParams pk{};
+    int dtype = GCNPT_F32;
+    int blocks = 0;
+};
+
+// sj from the trailing arguments of gcnpt_*_pack / gcnpt_*_packed, for a launch of `threads` per workgroup (enough workgroups for one
+// fragment per thread, at most 192).  optional (the _packed forms): n_layers <= 0 means no side job; otherwise n_layers is checked as
+// gcnpt_pack_weights_multi checks it
+static int side_job(SideJob& sj, bool optional, int threads, int n_layers, const float* const* W, const int* H, const int* Din, int dtype,
+                    void* const* w_fwd, void* const* w_bwd) {
+    sj = SideJob{};
+    sj.dtype = dtype;
+    if (optional && n_layers <= 0) return GCNPT_OK;
+    const int rc = fill_pack_params(sj.pk, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
+    if (rc != GCNPT_OK) return rc;
+    sj.blocks = (int)std::min<long long>(192, (sj.pk.first[n_layers] + threads - 1) / threads);
+    return GCNPT_OK;
+}
+
 static int prune_impl(void* stream, const int64_t* head, const int64_t* subj_pos, const int64_t* obj_pos,
                       const int64_t* deprel, const uint8_t* pad_mask, const int32_t* len, int B, int T,
                       int prune_k, int cap, int32_t* row_ptr, int32_t* col_idx, int32_t* label,
                       int32_t* rowT_ptr, int32_t* colT_idx, int32_t* ell, int32_t* ellT, uint8_t* pool_mask,
-                      int32_t* status, const PackParams& pk, int pk_dtype, int pack_blocks, const PackedOut& po = PackedOut{}) {
+                      int32_t* status, const SideJob& sj, const PackedOut& po = PackedOut{}) {
     GCNPT_REQUIRE(head && subj_pos && obj_pos && deprel && (pad_mask || len), "prune_to_csr: null input pointer");
     GCNPT_REQUIRE(row_ptr && col_idx && ell && status, "prune_to_csr: null output pointer");
     GCNPT_REQUIRE((rowT_ptr == nullptr) == (ellT == nullptr), "prune_to_csr: rowT_ptr, colT_idx and ellT go together");
@@ -1085,9 +1127,9 @@ static int prune_impl(void* stream, const int64_t* head, const int64_t* subj_pos
     // big batches, and sentences that occupy every wave of their workgroup: atomicMax per sentence (see the kernel)
     if ((long long)B * T > PRUNE_SCAN_MAX || (T > PRUNE_WAVE0_T && T + WAVE > PRUNE_THREADS))
         GCNPT_HIP_CHECK(hipMemsetAsync(status + B, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(prune_to_csr_kernel, dim3(B + pack_blocks), dim3(PRUNE_THREADS), lds, s, head, subj_pos, obj_pos, deprel,
+    hipLaunchKernelGGL(prune_to_csr_kernel, dim3(B + sj.blocks), dim3(PRUNE_THREADS), lds, s, head, subj_pos, obj_pos, deprel,
                        pad_mask, len, B, T, prune_k, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status,
-                       static_cast<unsigned long long*>(g_debug_stamps), pk, pk_dtype, staged, po);
+                       static_cast<unsigned long long*>(g_debug_stamps), sj.pk, sj.dtype, staged, po);
     GCNPT_HIP_CHECK(hipGetLastError());
     return GCNPT_OK;
 }
@@ -1098,12 +1140,7 @@ extern "C" int gcnpt_prune_to_csr(void* stream, const int64_t* head, const int64
                                   int32_t* rowT_ptr, int32_t* colT_idx, int32_t* ell, int32_t* ellT, uint8_t* pool_mask,
                                   int32_t* status) {
     return prune_impl(stream, head, subj_pos, obj_pos, deprel, pad_mask, len, B, T, prune_k, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx,
-                      ell, ellT, pool_mask, status, PackParams{}, GCNPT_F32, 0);
-}
-
-// workgroups a side-job pack adds to a launch of `threads` per workgroup: enough for one fragment per thread, at most 192
-static int pack_side_blocks(const PackParams& pk, int threads) {
-    return (int)std::min<long long>(192, (pk.first[pk.n_layers] + threads - 1) / threads);
+                      ell, ellT, pool_mask, status, SideJob{});
 }
 
 extern "C" int gcnpt_prune_to_csr_pack(void* stream, const int64_t* head, const int64_t* subj_pos, const int64_t* obj_pos,
@@ -1112,11 +1149,11 @@ extern "C" int gcnpt_prune_to_csr_pack(void* stream, const int64_t* head, const 
                                        int32_t* rowT_ptr, int32_t* colT_idx, int32_t* ell, int32_t* ellT, uint8_t* pool_mask,
                                        int32_t* status, int n_layers, const float* const* W, const int* H, const int* Din, int dtype,
                                        void* const* w_fwd, void* const* w_bwd) {
-    PackParams pk;
-    const int rc = fill_pack_params(pk, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
+    SideJob sj;
+    const int rc = side_job(sj, false, PRUNE_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
     if (rc != GCNPT_OK) return rc;
     return prune_impl(stream, head, subj_pos, obj_pos, deprel, pad_mask, len, B, T, prune_k, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx,
-                      ell, ellT, pool_mask, status, pk, dtype, pack_side_blocks(pk, PRUNE_THREADS));
+                      ell, ellT, pool_mask, status, sj);
 }
 
 // The pruner writing the token-packed layout itself (what gcnpt_pack_trees makes of gcnpt_prune_to_csr's arrays, bit for bit), optionally
@@ -1131,16 +1168,12 @@ extern "C" int gcnpt_prune_to_csr_packed(void* stream, const int64_t* head, cons
     GCNPT_REQUIRE(cu_seqlens && row_sent && status && sent_status && sync_ws && pool_mask, "prune_to_csr_packed: null pointer");
     GCNPT_REQUIRE(n_rows > 0 && nnz_cap > 0, "prune_to_csr_packed: n_rows and nnz_cap must be positive");
     GCNPT_REQUIRE(T <= 0xffff && 3 * (long long)T < (1 << 20), "prune_to_csr_packed: T=%d too long", T);
-    PackParams pk{};
-    int blocks = 0;
-    if (n_layers > 0) {
-        const int rc = fill_pack_params(pk, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
-        if (rc != GCNPT_OK) return rc;
-        blocks = pack_side_blocks(pk, PRUNE_THREADS);
-    }
+    SideJob sj;
+    const int rc = side_job(sj, true, PRUNE_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
+    if (rc != GCNPT_OK) return rc;
     PackedOut po{cu_seqlens, row_sent, pool_mask_padded, reinterpret_cast<unsigned long long*>(sync_ws), status, n_rows, nnz_cap};
     return prune_impl(stream, head, subj_pos, obj_pos, deprel, pad_mask, len, B, T, prune_k, 3 * T, row_ptr, col_idx, label, rowT_ptr, colT_idx,
-                      ell, ellT, pool_mask, sent_status, pk, dtype, blocks, po);
+                      ell, ellT, pool_mask, sent_status, sj, po);
 }
 
 extern "C" int gcnpt_adj_to_csr(void* stream, const float* adj, int B, int T, int cap, int32_t* row_ptr,
@@ -1178,23 +1211,19 @@ static int gather_impl(void* stream, const int32_t* src_row_ptr, const int32_t* 
                        const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* src_status,
                        const int32_t* src_len, int S, int Ts, int cap_s, const int64_t* idx, int B, int T, int cap,
                        int32_t* row_ptr, int32_t* col_idx, int32_t* label, int32_t* rowT_ptr, int32_t* colT_idx,
-                       int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status, const PackParams& pk, int pk_dtype, int pack_blocks) {
+                       int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status, const SideJob& sj) {
     GCNPT_REQUIRE(src_row_ptr && src_col_idx && src_ell && src_status && src_len && idx, "gather_trees: null cache pointer");
     GCNPT_REQUIRE(row_ptr && col_idx && ell && status, "gather_trees: null output pointer");
     GCNPT_REQUIRE(S > 0 && Ts > 0 && cap_s > 0 && B > 0 && T > 0 && cap > 0, "gather_trees: sizes must be positive");
-    GCNPT_REQUIRE(!label || src_label, "gather_trees: labels wanted but the cache holds none");
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr) && (rowT_ptr == nullptr) == (ellT == nullptr),
-                  "gather_trees: rowT_ptr, colT_idx and ellT go together");
-    GCNPT_REQUIRE(!rowT_ptr || (src_rowT_ptr && src_colT_idx && src_ellT), "gather_trees: transposed pattern wanted but the cache holds none");
-    GCNPT_REQUIRE(!pool_mask || src_pool_mask, "gather_trees: pool mask wanted but the cache holds none");
+    const int rc = check_request("gather_trees", src_label, src_rowT_ptr, src_colT_idx, src_ellT, src_pool_mask, label, rowT_ptr, colT_idx, ellT,
+                                 pool_mask);
+    if (rc != GCNPT_OK) return rc;
     if ((long long)B * cap > 0x7fffffffLL) return fail(GCNPT_E_UNSUPPORTED, "gather_trees: B*cap overflows int32");
-    const TreeArrays src{const_cast<int32_t*>(src_row_ptr), const_cast<int32_t*>(src_col_idx), const_cast<int32_t*>(src_label),
-                         const_cast<int32_t*>(rowT_ptr ? src_rowT_ptr : nullptr), const_cast<int32_t*>(src_colT_idx),
-                         const_cast<int32_t*>(src_ell), const_cast<int32_t*>(src_ellT), const_cast<uint8_t*>(src_pool_mask),
-                         const_cast<int32_t*>(src_status)};
+    const TreeArrays src = source_arrays(src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask,
+                                         src_status, rowT_ptr != nullptr);
     const TreeArrays dst{row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status};
-    hipLaunchKernelGGL(gather_trees_kernel, dim3(B + pack_blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, src, src_len, S, Ts, cap_s, idx,
-                       B, T, cap, dst, pk, pk_dtype);
+    hipLaunchKernelGGL(gather_trees_kernel, dim3(B + sj.blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, src, src_len, S, Ts, cap_s, idx,
+                       B, T, cap, dst, sj.pk, sj.dtype);
     GCNPT_HIP_CHECK(hipGetLastError());
     return GCNPT_OK;
 }
@@ -1207,7 +1236,7 @@ extern "C" int gcnpt_gather_trees(void* stream, const int32_t* src_row_ptr, cons
                                   int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status) {
     return gather_impl(stream, src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask, src_status,
                        src_len, S, Ts, cap_s, idx, B, T, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status,
-                       PackParams{}, GCNPT_F32, 0);
+                       SideJob{});
 }
 
 extern "C" int gcnpt_gather_trees_pack(void* stream, const int32_t* src_row_ptr, const int32_t* src_col_idx, const int32_t* src_label,
@@ -1218,12 +1247,11 @@ extern "C" int gcnpt_gather_trees_pack(void* stream, const int32_t* src_row_ptr,
                                        int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status, int n_layers,
                                        const float* const* W, const int* H, const int* Din, int dtype, void* const* w_fwd,
                                        void* const* w_bwd) {
-    PackParams pk;
-    const int rc = fill_pack_params(pk, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
+    SideJob sj;
+    const int rc = side_job(sj, false, GATHER_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
     if (rc != GCNPT_OK) return rc;
     return gather_impl(stream, src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask, src_status,
-                       src_len, S, Ts, cap_s, idx, B, T, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status,
-                       pk, dtype, pack_side_blocks(pk, GATHER_THREADS));
+                       src_len, S, Ts, cap_s, idx, B, T, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status, sj);
 }
 
 extern "C" int gcnpt_gather_trees_packed(void* stream, const int32_t* src_row_ptr, const int32_t* src_col_idx, const int32_t* src_label,
@@ -1238,25 +1266,18 @@ extern "C" int gcnpt_gather_trees_packed(void* stream, const int32_t* src_row_pt
     GCNPT_REQUIRE(src_row_ptr && src_col_idx && src_ell && src_status && src_len && src_pool_mask && idx, "gather_trees_packed: null cache pointer");
     GCNPT_REQUIRE(cu_seqlens && row_ptr && col_idx && ell && pool_mask && row_sent && status && sent_status, "gather_trees_packed: null output pointer");
     GCNPT_REQUIRE(S > 0 && Ts > 0 && cap_s > 0 && B > 0 && T > 0 && n_rows > 0 && nnz_cap > 0, "gather_trees_packed: sizes must be positive");
-    GCNPT_REQUIRE(!label || src_label, "gather_trees_packed: labels wanted but the cache holds none");
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr) && (rowT_ptr == nullptr) == (ellT == nullptr),
-                  "gather_trees_packed: rowT_ptr, colT_idx and ellT go together");
-    GCNPT_REQUIRE(!rowT_ptr || (src_rowT_ptr && src_colT_idx && src_ellT), "gather_trees_packed: transposed pattern wanted but the cache holds none");
-    PackParams pk{};
-    int blocks = 0;
-    if (n_layers > 0) {
-        const int rc = fill_pack_params(pk, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
-        if (rc != GCNPT_OK) return rc;
-        blocks = pack_side_blocks(pk, GATHER_THREADS);
-    }
-    const TreeArrays src{const_cast<int32_t*>(src_row_ptr), const_cast<int32_t*>(src_col_idx), const_cast<int32_t*>(src_label),
-                         const_cast<int32_t*>(rowT_ptr ? src_rowT_ptr : nullptr), const_cast<int32_t*>(src_colT_idx),
-                         const_cast<int32_t*>(src_ell), const_cast<int32_t*>(src_ellT), const_cast<uint8_t*>(src_pool_mask),
-                         const_cast<int32_t*>(src_status)};
+    int rc = check_request("gather_trees_packed", src_label, src_rowT_ptr, src_colT_idx, src_ellT, src_pool_mask, label, rowT_ptr, colT_idx, ellT,
+                           pool_mask);
+    if (rc != GCNPT_OK) return rc;
+    SideJob sj;
+    rc = side_job(sj, true, GATHER_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
+    if (rc != GCNPT_OK) return rc;
+    const TreeArrays src = source_arrays(src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask,
+                                         src_status, rowT_ptr != nullptr);
     const GatherPackedDst dst{cu_seqlens, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, pool_mask_padded, row_sent, status,
                               sent_status, n_rows, nnz_cap};
-    hipLaunchKernelGGL(gather_trees_packed_kernel, dim3(B + blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, src, src_len, S, Ts, cap_s, idx, B,
-                       T, dst, pk, dtype);
+    hipLaunchKernelGGL(gather_trees_packed_kernel, dim3(B + sj.blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, src, src_len, S, Ts, cap_s, idx,
+                       B, T, dst, sj.pk, sj.dtype);
     GCNPT_HIP_CHECK(hipGetLastError());
     return GCNPT_OK;
 }
@@ -1270,17 +1291,14 @@ extern "C" int gcnpt_compact_trees(void* stream, const int32_t* src_row_ptr, con
     GCNPT_REQUIRE(src_row_ptr && src_col_idx && src_ell && src_pool_mask && src_status, "compact_trees: null source pointer");
     GCNPT_REQUIRE(row_ptr && col_idx && ell && pool_mask && status && tok && kept, "compact_trees: null output pointer");
     GCNPT_REQUIRE(B > 0 && T > 0 && cap > 0 && Tc > 0 && cap_c > 0, "compact_trees: sizes must be positive");
-    GCNPT_REQUIRE(!label || src_label, "compact_trees: labels wanted but the source holds none");
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr) && (rowT_ptr == nullptr) == (ellT == nullptr),
-                  "compact_trees: rowT_ptr, colT_idx and ellT go together");
-    GCNPT_REQUIRE(!rowT_ptr || (src_rowT_ptr && src_colT_idx && src_ellT), "compact_trees: transposed pattern wanted but the source holds none");
+    const int rc = check_request("compact_trees", src_label, src_rowT_ptr, src_colT_idx, src_ellT, src_pool_mask, label, rowT_ptr, colT_idx, ellT,
+                                 pool_mask);
+    if (rc != GCNPT_OK) return rc;
     if ((long long)B * cap_c > 0x7fffffffLL) return fail(GCNPT_E_UNSUPPORTED, "compact_trees: B*cap_c overflows int32");
     const size_t lds = sizeof(int) * (size_t)T;
     if (lds > 60 * 1024) return fail(GCNPT_E_UNSUPPORTED, "compact_trees: T=%d exceeds the %d tokens a sentence may have", T, 60 * 1024 / 4);
-    const TreeArrays src{const_cast<int32_t*>(src_row_ptr), const_cast<int32_t*>(src_col_idx), const_cast<int32_t*>(src_label),
-                         const_cast<int32_t*>(rowT_ptr ? src_rowT_ptr : nullptr), const_cast<int32_t*>(src_colT_idx),
-                         const_cast<int32_t*>(src_ell), const_cast<int32_t*>(src_ellT), const_cast<uint8_t*>(src_pool_mask),
-                         const_cast<int32_t*>(src_status)};
+    const TreeArrays src = source_arrays(src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask,
+                                         src_status, rowT_ptr != nullptr);
     const TreeArrays dst{row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status};
     hipStream_t s = (hipStream_t)stream;
     GCNPT_HIP_CHECK(hipMemsetAsync(status + B, 0, sizeof(int32_t), s));         // status[B] = most kept tokens in a sentence (atomicMax)

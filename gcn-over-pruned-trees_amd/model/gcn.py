@@ -52,90 +52,15 @@ def _row_dims(h, trees, what):
     return trees.B, trees.T, trees.B * trees.T, (trees.B, trees.T)
 
 
-# ------------------------------------------------------------------------------------------------------
-# one GCN layer as an autograd op over the C-ABI
-# ------------------------------------------------------------------------------------------------------
-class _GCNLayerFn(torch.autograd.Function):
-    """out = dropout(relu((((A+I) h) W^T + 2 b) / (deg + 1)))  -- model/gcn.py:269-271, 390-393."""
-
-    @staticmethod
-    def forward(ctx, h, weight, bias, trees, drop_p, seed, compute, out_dtype, no_adj, seed_dev=None):
-        B, T, rows, lead = _row_dims(h, trees, "GCN layer")
-        Din = h.shape[-1]
-        H = weight.shape[0]
-        if weight.shape[1] != Din:
-            raise RuntimeError("GCN layer: input width %d does not match weight %s" % (Din, tuple(weight.shape)))
-        L = _lib.lib()
-        h = h.contiguous()
-        w32 = weight.detach().to(torch.float32).contiguous()
-        b32 = bias.detach().to(torch.float32).contiguous()
-        w_fwd = torch.empty((L.gcnpt_packed_bytes(H, Din, compute),), dtype=torch.uint8, device=h.device)
-        w_bwd = torch.empty((L.gcnpt_packed_bytes(Din, H, compute),), dtype=torch.uint8, device=h.device)
-        st = _lib.stream()
-        _lib.check(L.gcnpt_pack_weights(st, _lib.ptr(w32), H, Din, compute, _lib.ptr(w_fwd), _lib.ptr(w_bwd)))
-        out = torch.empty(lead + (H,), dtype=out_dtype, device=h.device)
-        g_ell = trees.empty_ell() if no_adj else trees.ell
-        # the gathered tile S = (A+I)h is saved in MFMA fragment order for the weight gradient (include/gcnpt.h)
-        want_wgrad = weight.requires_grad or bias.requires_grad
-        s_frag = torch.empty((L.gcnpt_frag_bytes(rows, Din, compute),), dtype=torch.uint8, device=h.device) if want_wgrad else None
-        _lib.check(L.gcnpt_layer_fwd(st, _lib.ptr(h), _lib.dtype_code(h.dtype), _lib.ptr(w_fwd), _lib.ptr(b32),
-                                     _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx), _lib.ptr(g_ell), _lib.ptr(trees.ell), B, T, Din, H,
-                                     _lib.ptr(out), _lib.dtype_code(out_dtype), compute, float(drop_p), int(seed), _lib.ptr(s_frag), _lib.ptr(seed_dev)))
-        ctx.save_for_backward(out, w_bwd, s_frag)
-        ctx.h_dtype = h.dtype
-        ctx.trees, ctx.no_adj, ctx.compute = trees, no_adj, compute
-        ctx.scale = 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0
-        ctx.dims = (B, T, Din, H)
-        ctx.rows, ctx.lead = rows, lead
-        ctx.param_dtypes = (weight.dtype, bias.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        out, w_bwd, s_frag = ctx.saved_tensors
-        trees, B, T, Din, H = ctx.trees, *ctx.dims
-        L, st = _lib.lib(), _lib.stream()
-        dev = out.device
-        gout = gout.to(out.dtype).contiguous()
-        gd = _lib.dtype_code(out.dtype)
-        dh = dW = db = z_frag = None
-        g_ellT = trees.empty_ell() if ctx.no_adj else trees.ellT
-        want_w = (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and s_frag is not None
-        if ctx.needs_input_grad[0]:
-            dh = torch.empty(ctx.lead + (Din,), dtype=ctx.h_dtype, device=dev)
-        if want_w:
-            z_frag = torch.empty((L.gcnpt_frag_bytes(ctx.rows, H, ctx.compute),), dtype=torch.uint8, device=dev)
-            dW = torch.empty((H, Din), dtype=torch.float32, device=dev)     # cleared by bwd_data, filled by bwd_weight
-            db = torch.empty((H,), dtype=torch.float32, device=dev)
-        if dh is not None or want_w:
-            _lib.check(L.gcnpt_layer_bwd_data(st, _lib.ptr(gout), _lib.ptr(out), gd, _lib.ptr(w_bwd), _lib.ptr(trees.ell),
-                                              _lib.ptr(trees.rowT_ptr), _lib.ptr(trees.colT_idx), _lib.ptr(g_ellT), B, T, Din, H, _lib.ptr(dh),
-                                              _lib.dtype_code(ctx.h_dtype), ctx.compute, ctx.scale, _lib.ptr(z_frag),
-                                              _lib.ptr(dW), _lib.ptr(db), None, 1.0, 0))
-        if want_w:
-            _lib.check(L.gcnpt_layer_bwd_weight(st, _lib.ptr(z_frag), _lib.ptr(s_frag), B, T, Din, H, _lib.ptr(dW), _lib.ptr(db),
-                                                ctx.compute))
-            dW, db = dW.to(ctx.param_dtypes[0]), db.to(ctx.param_dtypes[1])
-        return dh, dW, db, None, None, None, None, None, None, None
-
-
 def gcn_layer(h, weight, bias, trees, drop_p=0.0, seed=0, compute_dtype=torch.float32, out_dtype=None, no_adj=False, seed_dev=None):
     """
-    Functional form of one iteration of the reference's layer loop.  h [B,T,Din] (float32 or bfloat16, CUDA),
-    weight [H,Din], bias [H] (nn.Linear layout), trees: PrunedTrees.  compute_dtype float32 = exact fp32 MFMA,
-    bfloat16 = bf16 operands with fp32 accumulation.  seed_dev: optional int64 [1] CUDA tensor added to `seed` on the device
-    (advance it between replays of a captured graph to get fresh dropout masks).
+    Functional form of one iteration of the reference's layer loop: out = dropout(relu((((A+I) h) W^T + 2 b) / (deg + 1)))
+    (model/gcn.py:269-271, 390-393), as a one-layer gcn_layers.  h [B,T,Din] (float32 or bfloat16, CUDA), weight [H,Din],
+    bias [H] (nn.Linear layout), trees: PrunedTrees.  compute_dtype float32 = exact fp32 MFMA, bfloat16 = bf16 operands with
+    fp32 accumulation; out_dtype (default: h's) is float32 whenever compute_dtype is.  seed_dev: optional int64 [1] CUDA tensor
+    added to `seed` on the device (advance it between replays of a captured graph to get fresh dropout masks).
     """
-    if not isinstance(trees, (PrunedTrees, PackedTrees)):
-        raise TypeError("trees must be a PrunedTrees (see model.tree.prune_to_csr / adj_to_csr) or a PackedTrees (PrunedTrees.pack)")
-    compute = _lib.dtype_code(compute_dtype)
-    _lib.require_gpu(h)
-    if compute == _lib.F32 and h.dtype != torch.float32:
-        h = h.float()
-    out_dtype = out_dtype or h.dtype
-    if compute == _lib.F32:
-        out_dtype = torch.float32
-    return _GCNLayerFn.apply(h, weight, bias, trees, float(drop_p), int(seed), compute, out_dtype, bool(no_adj), seed_dev)
+    return gcn_layers(h, [weight], [bias], trees, [drop_p], [seed], compute_dtype, out_dtype or h.dtype, no_adj, seed_dev)
 
 
 class WeightPack(object):
@@ -741,6 +666,9 @@ class GCN(nn.Module):
 
         packed = adj if isinstance(adj, PackedTrees) else None
         if packed is not None and self.adj_type != 'regular':
+            if not isinstance(packed.padded, PrunedTrees):
+                raise ValueError("adj_type %r runs on the padded adjacency, which trees pruned straight into the packed layout "
+                                 "(prune_to_csr_packed, TreeCache.batch_packed) do not keep: use prune_to_csr(...).pack(...)" % self.adj_type)
             adj = packed.padded                                  # the deprel variants run on the padded layout
         if self.adj_type == 'diagonal_deprel':
             return self._forward_diagonal(adj, gcn_inputs, deprel)

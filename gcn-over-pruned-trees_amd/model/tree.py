@@ -38,6 +38,19 @@ class TreeError(ValueError):
                          % (self.sentence, self.code, self.reference))
 
 
+def _check_status(status, expect_maxlen):
+    """Synchronises on a [B+1] status array and raises what the reference would have raised while building the trees."""
+    st = status.cpu()
+    bad = torch.nonzero(st[:-1] != 0)
+    if bad.numel():
+        b = int(bad[0])
+        raise TreeError(b, int(st[b]))
+    if expect_maxlen is not None and int(st[-1]) != expect_maxlen:
+        raise ValueError("longest sentence has %d tokens but the batch is padded to %d: the reference builds "
+                         "adj as [B,%d,%d] and its bmm with [B,%d,D] inputs fails (model/gcn.py:97,269)"
+                         % (int(st[-1]), expect_maxlen, int(st[-1]), int(st[-1]), expect_maxlen))
+
+
 class PrunedTrees(object):
     """
     CSR pattern of the batch adjacency in HBM (layout: include/gcnpt.h).
@@ -73,16 +86,14 @@ class PrunedTrees(object):
         Synchronises and raises what the reference would have raised while building the trees.
         expect_maxlen: the padded length T; the reference's bmm fails when max(len) != T (gcn.py:97,269).
         """
-        st = self.status.cpu()
-        bad = torch.nonzero(st[:-1] != 0)
-        if bad.numel():
-            b = int(bad[0])
-            raise TreeError(b, int(st[b]))
-        if expect_maxlen is not None and int(st[-1]) != expect_maxlen:
-            raise ValueError("longest sentence has %d tokens but the batch is padded to %d: the reference builds "
-                             "adj as [B,%d,%d] and its bmm with [B,%d,D] inputs fails (model/gcn.py:97,269)"
-                             % (int(st[-1]), expect_maxlen, int(st[-1]), int(st[-1]), expect_maxlen))
+        _check_status(self.status, expect_maxlen)
         return self
+
+    def c_args(self):
+        """The nine arrays as C-ABI pointers, in include/gcnpt.h's order (row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT,
+        pool_mask, status); NULL for the ones this batch does not hold."""
+        return tuple(_lib.ptr(a) for a in (self.row_ptr, self.col_idx, self.label, self.rowT_ptr, self.colT_idx, self.ell, self.ellT,
+                                           self.pool_mask, self.status))
 
     def nnz(self):
         rp = self.row_ptr.view(self.B, self.T + 1)
@@ -105,20 +116,17 @@ class PrunedTrees(object):
             Tc = max(int((~src_mask.view(self.B, self.T)).sum(1).max()), 1)
         Tc = int(Tc)
         cap_c = 3 * Tc if self.cap == 3 * self.T else min(self.cap, Tc * Tc)
-        bufs = _alloc(self.B, Tc, cap_c, self.device, self.label is not None, self.rowT_ptr is not None)
-        row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status = bufs
+        out = _alloc(self.B, Tc, cap_c, self.device, self.label is not None, self.rowT_ptr is not None)
         tok = torch.empty((self.B, Tc), dtype=torch.int64, device=self.device)
         kept = torch.empty((self.B,), dtype=torch.int32, device=self.device)
-        P = _lib.ptr
-        _lib.check(_lib.lib().gcnpt_compact_trees(
-            _lib.stream(), P(self.row_ptr), P(self.col_idx), P(self.label), P(self.rowT_ptr), P(self.colT_idx), P(self.ell), P(self.ellT),
-            P(src_mask), P(self.status), self.B, self.T, self.cap, Tc, cap_c, P(row_ptr), P(col_idx), P(label), P(rowT_ptr),
-            P(colT_idx), P(ell), P(ellT), P(pool_mask), P(status), P(tok), P(kept)))
+        src = self.c_args()
+        _lib.check(_lib.lib().gcnpt_compact_trees(_lib.stream(), *src[:7], _lib.ptr(src_mask), src[8], self.B, self.T, self.cap, Tc, cap_c,
+                                                  *out.c_args(), _lib.ptr(tok), _lib.ptr(kept)))
         if also_keep is not None:
             # the extra tokens are rows of the compact batch but NOT members of the tree: the mask GCN.forward returns stays the reference's
             orig = torch.gather(self.pool_mask.view(self.B, self.T), 1, tok.clamp(min=0))
-            pool_mask.copy_((orig | (tok < 0)).view(self.B, Tc, 1))
-        return CompactTrees(PrunedTrees(self.B, Tc, cap_c, *bufs), tok, kept, self.T)
+            out.pool_mask.copy_((orig | (tok < 0)).view(self.B, Tc, 1))
+        return CompactTrees(out, tok, kept, self.T)
 
     def pack(self, lens, n_rows=None):
         """
@@ -127,39 +135,17 @@ class PrunedTrees(object):
         list avoids the one sync that sizing the packed buffers otherwise needs -- the reference itself syncs for the lengths
         at this point, model/gcn.py:96); n_rows: rows to allocate if the caller knows sum(lens).  Returns a PackedTrees.
         """
-        dev = self.device
-        lens_dev = torch.as_tensor(lens, device=dev).to(torch.int32).contiguous()
-        if lens_dev.numel() != self.B:
-            raise ValueError("pack: %d lengths for %d sentences" % (lens_dev.numel(), self.B))
-        if n_rows is None:
-            n_rows = int(sum(int(v) for v in lens)) if not torch.is_tensor(lens) or not lens.is_cuda else int(lens_dev.clamp(max=self.T).sum().item())
-        n_rows = max(int(n_rows), 1)
+        lens_dev, n_rows = _packed_rows("pack", lens, self.B, self.T, self.device, n_rows)
         nnz_cap = min(self.B * self.cap, max(3 * n_rows, 1)) if self.cap == 3 * self.T else self.B * self.cap
-        i32 = dict(dtype=torch.int32, device=dev)
-        tr = self.rowT_ptr is not None
-        cu = torch.empty((self.B + 1,), **i32)
-        row_ptr = torch.empty((n_rows + 1,), **i32)
-        col_idx = torch.empty((nnz_cap,), **i32)
-        label = torch.empty((nnz_cap,), **i32) if self.label is not None else None
-        rowT_ptr = torch.empty((n_rows + 1,), **i32) if tr else None
-        colT_idx = torch.empty((nnz_cap,), **i32) if tr else None
-        ell = torch.zeros((n_rows * 8,), **i32)
-        ellT = torch.zeros((n_rows * 8,), **i32) if tr else None
-        pool_mask = torch.ones((n_rows, 1), dtype=torch.bool, device=dev)
-        row_sent = torch.zeros((n_rows,), **i32)
-        status = torch.empty((2,), **i32)
-        P = _lib.ptr
-        _lib.check(_lib.lib().gcnpt_pack_trees(
-            _lib.stream(), P(self.row_ptr), P(self.col_idx), P(self.label), P(self.rowT_ptr), P(self.colT_idx), P(self.ell), P(self.ellT),
-            P(self.pool_mask), P(lens_dev), self.B, self.T, self.cap, P(cu), P(row_ptr), P(col_idx), P(label), P(rowT_ptr), P(colT_idx),
-            P(ell), P(ellT), P(pool_mask), P(row_sent), n_rows, nnz_cap, P(status)))
-        return PackedTrees(self, n_rows, nnz_cap, cu, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, row_sent, status)
+        out = _alloc_packed(self, n_rows, nnz_cap, self.label is not None, self.rowT_ptr is not None)
+        # the source's arrays with the lengths where its status would go (include/gcnpt.h, gcnpt_pack_trees)
+        _lib.check(_lib.lib().gcnpt_pack_trees(_lib.stream(), *self.c_args()[:-1], _lib.ptr(lens_dev), self.B, self.T, self.cap, *out.c_args()))
+        return out
 
     def to_dense(self):
         """float32 [B,T,T] with the labels tree_to_adj writes (deprel id, +42 for the reverse edge, 84 on the diagonal)."""
         adj = torch.empty((self.B, self.T, self.T), dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().gcnpt_csr_to_adj(_lib.stream(), _lib.ptr(self.row_ptr), _lib.ptr(self.col_idx),
-                                               _lib.ptr(self.label), self.B, self.T, _lib.ptr(adj)))
+        _lib.check(_lib.lib().gcnpt_csr_to_adj(_lib.stream(), *self.c_args()[:3], self.B, self.T, _lib.ptr(adj)))
         return adj
 
 
@@ -201,6 +187,12 @@ class PackedTrees(object):
         if int(st[1]) != self.N:
             raise ValueError("pack_trees: sum(len) = %d but %d rows were allocated" % (int(st[1]), self.N))
         return self
+
+    def c_args(self):
+        """The packed arrays as the C-ABI's packed forms take them: cu_seqlens, row_ptr ... pool_mask, row_sent, n_rows, nnz_cap, status."""
+        P = _lib.ptr
+        return (P(self.cu_seqlens), P(self.row_ptr), P(self.col_idx), P(self.label), P(self.rowT_ptr), P(self.colT_idx), P(self.ell),
+                P(self.ellT), P(self.pool_mask), P(self.row_sent), self.N, self.nnz_cap, P(self.status))
 
     def pack_rows(self, t):
         """[B,T,W] (or [B,T]) -> packed [N,W] ([N]); differentiable."""
@@ -301,16 +293,66 @@ class CompactTrees(object):
 
 def _alloc(B, T, cap, device, want_label, want_transpose):
     i32 = dict(dtype=torch.int32, device=device)
-    row_ptr = torch.empty((B * (T + 1),), **i32)
-    col_idx = torch.empty((B * cap,), **i32)
-    label = torch.empty((B * cap,), **i32) if want_label else None
-    rowT_ptr = torch.empty((B * (T + 1),), **i32) if want_transpose else None
-    colT_idx = torch.empty((B * cap,), **i32) if want_transpose else None
-    ell = torch.empty((B * T * 8,), **i32)
-    ellT = torch.empty((B * T * 8,), **i32) if want_transpose else None
-    pool_mask = torch.empty((B, T, 1), dtype=torch.bool, device=device)
-    status = torch.empty((B + 1,), **i32)
-    return row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status
+    return PrunedTrees(B, T, cap,
+                       torch.empty((B * (T + 1),), **i32),                                  # row_ptr
+                       torch.empty((B * cap,), **i32),                                      # col_idx
+                       torch.empty((B * cap,), **i32) if want_label else None,              # label
+                       torch.empty((B * (T + 1),), **i32) if want_transpose else None,      # rowT_ptr
+                       torch.empty((B * cap,), **i32) if want_transpose else None,          # colT_idx
+                       torch.empty((B * T * 8,), **i32),                                    # ell
+                       torch.empty((B * T * 8,), **i32) if want_transpose else None,        # ellT
+                       torch.empty((B, T, 1), dtype=torch.bool, device=device),             # pool_mask
+                       torch.empty((B + 1,), **i32))                                        # status
+
+
+def _alloc_packed(padded, n_rows, nnz_cap, want_label, want_transpose):
+    """The buffers of a PackedTrees over `padded`'s batch.  The kernels leave rows past cu_seqlens[B] unwritten, so ell / ellT / row_sent
+    start as zeros and pool_mask as ones (an empty row outside every tree)."""
+    i32 = dict(dtype=torch.int32, device=padded.device)
+    return PackedTrees(padded, n_rows, nnz_cap,
+                       torch.empty((padded.B + 1,), **i32),                                 # cu_seqlens
+                       torch.empty((n_rows + 1,), **i32),                                   # row_ptr
+                       torch.empty((nnz_cap,), **i32),                                      # col_idx
+                       torch.empty((nnz_cap,), **i32) if want_label else None,              # label
+                       torch.empty((n_rows + 1,), **i32) if want_transpose else None,       # rowT_ptr
+                       torch.empty((nnz_cap,), **i32) if want_transpose else None,          # colT_idx
+                       torch.zeros((n_rows * 8,), **i32),                                   # ell
+                       torch.zeros((n_rows * 8,), **i32) if want_transpose else None,       # ellT
+                       torch.ones((n_rows, 1), dtype=torch.bool, device=padded.device),     # pool_mask
+                       torch.zeros((n_rows,), **i32),                                       # row_sent
+                       torch.empty((2,), **i32))                                            # status
+
+
+def _packed_rows(what, lens, B, T, device, n_rows):
+    """lens as an int32 device tensor, and the rows a packed batch of those lengths needs: n_rows if the caller knows it, else sum(lens)
+    (host lengths) or sum(min(len, T)) (device lengths: one sync); at least 1."""
+    lens_dev = torch.as_tensor(lens, device=device).to(torch.int32).contiguous()
+    if lens_dev.numel() != B:
+        raise ValueError("%s: %d lengths for %d sentences" % (what, lens_dev.numel(), B))
+    if n_rows is None:
+        n_rows = int(sum(int(v) for v in lens)) if not torch.is_tensor(lens) or not lens.is_cuda else int(lens_dev.clamp(max=T).sum().item())
+    return lens_dev, max(int(n_rows), 1)
+
+
+def _pad_mask(masks, B, T):
+    """The pad mask (True = pad) as the C-ABI takes it, or None."""
+    if masks is None:
+        return None
+    masks = masks.contiguous()
+    if masks.dtype not in (torch.bool, torch.uint8) or tuple(masks.shape) != (B, T):
+        raise TypeError("masks must be bool/uint8 [B,T]")
+    return masks
+
+
+_NO_PACK = (0, None, None, None, 0, None, None)     # the weight-pack tail of a gcnpt_*_packed launch without the side job (n_layers = 0)
+
+
+def _launch(entry, args, pack, no_pack=()):
+    """entry(*args, <weight-pack tail>): pack is a model.gcn.WeightPack whose images the launch fills as a side job, or None (the tail
+    is then `no_pack`).  Marks the request launched."""
+    _lib.check(entry(*args, *(pack.c_args() if pack is not None else no_pack)))
+    if pack is not None:
+        pack.launched = True
 
 
 def _i64(t, name):
@@ -335,37 +377,36 @@ def prune_to_csr(head, subj_pos, obj_pos, deprel, prune_k, masks=None, lens=None
     B, T = head.shape
     if masks is None and lens is None:
         raise ValueError("give masks (True = pad) or lens")
-    if masks is not None:
-        masks = masks.contiguous()
-        if masks.dtype not in (torch.bool, torch.uint8) or tuple(masks.shape) != (B, T):
-            raise TypeError("masks must be bool/uint8 [B,T]")
+    masks = _pad_mask(masks, B, T)
     if lens is not None:
         lens = lens.to(device=head.device, dtype=torch.int32).contiguous()
     cap = 3 * T
-    bufs = _alloc(B, T, cap, head.device, want_label, bool(want_transpose))
-    row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status = bufs
-    args = (_lib.stream(), _lib.ptr(head), _lib.ptr(subj_pos), _lib.ptr(obj_pos), _lib.ptr(deprel),
-            _lib.ptr(masks) if masks is not None else None, _lib.ptr(lens) if masks is None else None,
-            B, T, int(prune_k), cap, _lib.ptr(row_ptr), _lib.ptr(col_idx), _lib.ptr(label), _lib.ptr(rowT_ptr),
-            _lib.ptr(colT_idx), _lib.ptr(ell), _lib.ptr(ellT), _lib.ptr(pool_mask), _lib.ptr(status))
-    if pack is None:
-        _lib.check(_lib.lib().gcnpt_prune_to_csr(*args))
-    else:
-        _lib.check(_lib.lib().gcnpt_prune_to_csr_pack(*(args + pack.c_args())))
-        pack.launched = True
-    return PrunedTrees(B, T, cap, *bufs)
+    out = _alloc(B, T, cap, head.device, want_label, bool(want_transpose))
+    P = _lib.ptr
+    args = (_lib.stream(), P(head), P(subj_pos), P(obj_pos), P(deprel), P(masks), P(lens) if masks is None else None, B, T, int(prune_k), cap,
+            *out.c_args())
+    lib = _lib.lib()
+    _launch(lib.gcnpt_prune_to_csr if pack is None else lib.gcnpt_prune_to_csr_pack, args, pack)
+    return out
 
 
-class _PaddedInfo(PrunedTrees):
+class _PaddedInfo(object):
     """What a batch pruned straight into the packed layout keeps of the padded one: its shape, the per-sentence status and the
-    padded pool mask (what GCN.forward returns); no adjacency arrays."""
+    padded pool mask (what GCN.forward returns), for the launch to fill.  It holds no adjacency: it is not a PrunedTrees."""
 
-    def __init__(self, B, T, pool_mask, status):
-        super().__init__(B, T, 3 * T, None, None, None, None, None, None, None, pool_mask, status)
+    def __init__(self, B, T, device, want_pool_mask):
+        self.B, self.T = B, T
+        self.pool_mask = torch.empty((B, T, 1), dtype=torch.bool, device=device) if want_pool_mask else None
+        self.status = torch.empty((B + 1,), dtype=torch.int32, device=device)
 
     @property
     def device(self):
         return self.status.device
+
+    def check(self, expect_maxlen=None):
+        """As PrunedTrees.check."""
+        _check_status(self.status, expect_maxlen)
+        return self
 
 
 _SYNC_WS = {}        # (device, stream) -> zeroed uint64 workspace of gcnpt_prune_to_csr_packed (left zero by every launch)
@@ -384,46 +425,19 @@ def prune_to_csr_packed(head, subj_pos, obj_pos, deprel, prune_k, lens, masks=No
     head, subj_pos, obj_pos, deprel = (_i64(t, n) for t, n in ((head, "head"), (subj_pos, "subj_pos"), (obj_pos, "obj_pos"), (deprel, "deprel")))
     B, T = head.shape
     dev = head.device
-    lens_dev = torch.as_tensor(lens, device=dev).to(torch.int32).contiguous()
-    if lens_dev.numel() != B:
-        raise ValueError("prune_to_csr_packed: %d lengths for %d sentences" % (lens_dev.numel(), B))
-    if n_rows is None:
-        n_rows = int(sum(int(v) for v in lens)) if not torch.is_tensor(lens) or not lens.is_cuda else int(lens_dev.clamp(max=T).sum().item())
-    n_rows = max(int(n_rows), 1)
-    nnz_cap = max(3 * n_rows, 1)
-    if masks is not None:
-        masks = masks.contiguous()
-        if masks.dtype not in (torch.bool, torch.uint8) or tuple(masks.shape) != (B, T):
-            raise TypeError("masks must be bool/uint8 [B,T]")
-    i32 = dict(dtype=torch.int32, device=dev)
-    tr = bool(want_transpose)
-    cu = torch.empty((B + 1,), **i32)
-    row_ptr = torch.empty((n_rows + 1,), **i32)
-    col_idx = torch.empty((nnz_cap,), **i32)
-    label = torch.empty((nnz_cap,), **i32) if want_label else None
-    rowT_ptr = torch.empty((n_rows + 1,), **i32) if tr else None
-    colT_idx = torch.empty((nnz_cap,), **i32) if tr else None
-    ell = torch.zeros((n_rows * 8,), **i32)
-    ellT = torch.zeros((n_rows * 8,), **i32) if tr else None
-    pool_mask = torch.ones((n_rows, 1), dtype=torch.bool, device=dev)
-    row_sent = torch.zeros((n_rows,), **i32)
-    status = torch.empty((2,), **i32)
-    sent_status = torch.empty((B + 1,), **i32)
-    pm_padded = torch.empty((B, T, 1), dtype=torch.bool, device=dev) if want_padded_mask else None
+    lens_dev, n_rows = _packed_rows("prune_to_csr_packed", lens, B, T, dev, n_rows)
+    masks = _pad_mask(masks, B, T)
+    padded = _PaddedInfo(B, T, dev, want_padded_mask)
+    out = _alloc_packed(padded, n_rows, max(3 * n_rows, 1), want_label, bool(want_transpose))
     key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
     ws = _SYNC_WS.get(key)
     if ws is None or ws.numel() < B + 2:
         ws = _SYNC_WS[key] = torch.zeros((max(B + 2, 1024),), dtype=torch.int64, device=dev)
     P = _lib.ptr
-    tail = pack.c_args() if pack is not None else (0, None, None, None, 0, None, None)
-    _lib.check(_lib.lib().gcnpt_prune_to_csr_packed(
-        _lib.stream(), P(head), P(subj_pos), P(obj_pos), P(deprel), P(masks) if masks is not None else None, P(lens_dev) if masks is None else None,
-        B, T, int(prune_k), P(cu), P(row_ptr), P(col_idx), P(label), P(rowT_ptr), P(colT_idx), P(ell), P(ellT), P(pool_mask), P(row_sent),
-        n_rows, nnz_cap, P(status), P(sent_status), P(pm_padded), P(ws), *tail))
-    if pack is not None:
-        pack.launched = True
-    padded = _PaddedInfo(B, T, pm_padded, sent_status)
-    return PackedTrees(padded, n_rows, nnz_cap, cu, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, row_sent, status)
+    args = (_lib.stream(), P(head), P(subj_pos), P(obj_pos), P(deprel), P(masks), P(lens_dev) if masks is None else None, B, T, int(prune_k),
+            *out.c_args(), P(padded.status), P(padded.pool_mask), P(ws))
+    _launch(_lib.lib().gcnpt_prune_to_csr_packed, args, pack, _NO_PACK)
+    return out
 
 
 def adj_to_csr(adj, want_label=True):
@@ -433,12 +447,9 @@ def adj_to_csr(adj, want_label=True):
     adj = _lib.require_gpu(adj).contiguous()
     B, T, _ = adj.shape
     cap = T * T
-    bufs = _alloc(B, T, cap, adj.device, want_label, True)
-    row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status = bufs
-    _lib.check(_lib.lib().gcnpt_adj_to_csr(_lib.stream(), _lib.ptr(adj), B, T, cap, _lib.ptr(row_ptr), _lib.ptr(col_idx),
-                                           _lib.ptr(label), _lib.ptr(rowT_ptr), _lib.ptr(colT_idx), _lib.ptr(ell), _lib.ptr(ellT),
-                                           _lib.ptr(pool_mask), _lib.ptr(status)))
-    return PrunedTrees(B, T, cap, *bufs)
+    out = _alloc(B, T, cap, adj.device, want_label, True)
+    _lib.check(_lib.lib().gcnpt_adj_to_csr(_lib.stream(), _lib.ptr(adj), B, T, cap, *out.c_args()))
+    return out
 
 
 class TreeCache(object):
@@ -501,33 +512,12 @@ class TreeCache(object):
             ok = (idx >= 0) & (idx < len(self))
             n_rows = int((self.lens.index_select(0, idx.clamp(0, len(self) - 1)).clamp(max=T) * ok).sum().item())
         n_rows = max(int(n_rows), 1)
-        nnz_cap = max(3 * n_rows, 1)
-        dev = src.device
-        i32 = dict(dtype=torch.int32, device=dev)
-        cu = torch.empty((B + 1,), **i32)
-        row_ptr = torch.empty((n_rows + 1,), **i32)
-        col_idx = torch.empty((nnz_cap,), **i32)
-        label = torch.empty((nnz_cap,), **i32) if want_label else None
-        rowT_ptr = torch.empty((n_rows + 1,), **i32) if tr else None
-        colT_idx = torch.empty((nnz_cap,), **i32) if tr else None
-        ell = torch.zeros((n_rows * 8,), **i32)
-        ellT = torch.zeros((n_rows * 8,), **i32) if tr else None
-        pool_mask = torch.ones((n_rows, 1), dtype=torch.bool, device=dev)
-        row_sent = torch.zeros((n_rows,), **i32)
-        status = torch.empty((2,), **i32)
-        sent_status = torch.empty((B + 1,), **i32)
-        pm_padded = torch.empty((B, T, 1), dtype=torch.bool, device=dev) if want_padded_mask else None
+        out = _alloc_packed(_PaddedInfo(B, T, src.device, want_padded_mask), n_rows, max(3 * n_rows, 1), want_label, tr)
         P = _lib.ptr
-        tail = pack.c_args() if pack is not None else (0, None, None, None, 0, None, None)
-        _lib.check(_lib.lib().gcnpt_gather_trees_packed(
-            _lib.stream(), P(src.row_ptr), P(src.col_idx), P(src.label), P(src.rowT_ptr), P(src.colT_idx), P(src.ell), P(src.ellT),
-            P(src.pool_mask), P(src.status), P(self.lens), src.B, src.T, src.cap, P(idx), B, T,
-            P(cu), P(row_ptr), P(col_idx), P(label), P(rowT_ptr), P(colT_idx), P(ell), P(ellT), P(pool_mask), P(row_sent),
-            n_rows, nnz_cap, P(status), P(sent_status), P(pm_padded), *tail))
-        if pack is not None:
-            pack.launched = True
-        return PackedTrees(_PaddedInfo(B, T, pm_padded, sent_status), n_rows, nnz_cap, cu, row_ptr, col_idx, label, rowT_ptr, colT_idx,
-                           ell, ellT, pool_mask, row_sent, status)
+        args = (_lib.stream(), *src.c_args(), P(self.lens), src.B, src.T, src.cap, P(idx), B, T, *out.c_args(), P(out.padded.status),
+                P(out.padded.pool_mask))
+        _launch(_lib.lib().gcnpt_gather_trees_packed, args, pack, _NO_PACK)
+        return out
 
     @staticmethod
     def _gather(src, lens, idx, T, want_label, pack=None):
@@ -536,18 +526,11 @@ class TreeCache(object):
         if want_label and src.label is None:
             raise ValueError("the cache was built without labels")
         cap = 3 * T
-        bufs = _alloc(B, T, cap, src.device, want_label, True)
-        row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status = bufs
-        P = _lib.ptr
-        args = (_lib.stream(), P(src.row_ptr), P(src.col_idx), P(src.label), P(src.rowT_ptr), P(src.colT_idx), P(src.ell), P(src.ellT),
-                P(src.pool_mask), P(src.status), P(lens), src.B, src.T, src.cap, P(idx), B, T, cap,
-                P(row_ptr), P(col_idx), P(label), P(rowT_ptr), P(colT_idx), P(ell), P(ellT), P(pool_mask), P(status))
-        if pack is None:
-            _lib.check(_lib.lib().gcnpt_gather_trees(*args))
-        else:
-            _lib.check(_lib.lib().gcnpt_gather_trees_pack(*(args + pack.c_args())))
-            pack.launched = True
-        return PrunedTrees(B, T, cap, *bufs)
+        out = _alloc(B, T, cap, src.device, want_label, True)
+        args = (_lib.stream(), *src.c_args(), _lib.ptr(lens), src.B, src.T, src.cap, _lib.ptr(idx), B, T, cap, *out.c_args())
+        lib = _lib.lib()
+        _launch(lib.gcnpt_gather_trees if pack is None else lib.gcnpt_gather_trees_pack, args, pack)
+        return out
 
 
 def inputs_to_tree_reps(head, words, l, prune, subj_pos, obj_pos, deprel):

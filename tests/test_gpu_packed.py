@@ -385,3 +385,28 @@ def test_classifier_packed_matches_golden_logits(api, dev, fixture):
     with torch.no_grad():
         logits_c, pooled_c = model(inputs, trees=cache.batch_packed(ids, head.shape[1], n_rows=int(lens.sum())))
     assert np.array_equal(logits_c.cpu().numpy(), outs[True][0]) and np.array_equal(pooled_c.cpu().numpy(), outs[True][1])
+
+
+def test_deprel_model_refuses_trees_pruned_straight_into_packed_layout(api, dev):
+    """The deprel variants run on the padded adjacency: PackedTrees from TreeCache.batch_packed keep none, and the model says so (ValueError);
+    the two-step form batch(...).pack(...) keeps it and gives the model's own logits."""
+    import json
+    gcn, tree = api
+    g = load_golden("e2e_diag.npz")
+    opt = json.loads(str(g["opt"]))
+    opt["cuda"] = True
+    model = gcn.GCNClassifier(opt)
+    model.load_state_dict({k[3:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("sd:")}, strict=True)
+    model.to(dev).eval()
+    inputs = tuple(_t(g[k], dev) for k in ("words", "masks", "pos", "ner", "deprel", "head", "subj_pos", "obj_pos"))
+    head, subj, obj, dep, masks = (_t(g[k], dev) for k in ("head", "subj_pos", "obj_pos", "deprel", "masks"))
+    lens = (~masks.bool()).sum(1).to(torch.int32)
+    cache = tree.TreeCache.build(head, subj, obj, dep, opt["prune_k"], lens=lens, want_label=True)
+    ids = torch.arange(head.shape[0], device=dev)
+    T = head.shape[1]
+    with torch.no_grad():
+        with pytest.raises(ValueError, match=r"prune_to_csr\(\.\.\.\)\.pack"):
+            model(inputs, trees=cache.batch_packed(ids, T, n_rows=int(lens.sum())))
+        logits, _ = model(inputs)
+        logits_p, _ = model(inputs, trees=cache.batch(ids, T).pack(lens.tolist()))
+    assert max_rel(logits_p.cpu().numpy(), logits.cpu().numpy()) <= 1e-5
