@@ -344,6 +344,65 @@ struct SideWgrad { const SideWgrads* sw = nullptr; bool carried = false; };
 extern thread_local SideWgrad t_side;      // defined in rowtile_kernels.hip
 
 
+// Big batches (more row tiles than CUs): workgroups of 4 waves, two or three per CU, so that one workgroup's memory waits overlap another's
+// arithmetic (the 8-wave form keeps ~240 registers per wave: one workgroup per CU, nothing to overlap with).  Measured (C2 widths,
+// B = 64 ... 1024; C5 widths): slower below ~256 tiles (B = 80: +20 %), 3 % faster at B = 100, 9-12 % faster from B = 256 on and at the
+// C5 shape; not when the narrower workgroup needs one more column pass than the wide one (360 columns: 23 tiles = 20 + 3).
+// gcnpt_set_option(GCNPT_OPT_FOUR_WAVES, 0 / 1) forces the choice (A/B, tests).
+static inline bool use_four_waves(const RowTileParams& p) {
+    const int forced = option(GCNPT_OPT_FOUR_WAVES);
+    if (forced == 0 || forced == 1) return forced == 1;
+    if (ceil_div(p.N, ROWS) <= 256) return false;
+    const int n_tiles = ceil_div(p.NOUT, 16);
+    const int pass8 = n_tiles <= 24 ? 1 : ceil_div(n_tiles, 32), pass4 = n_tiles <= 24 ? 1 : ceil_div(n_tiles, 20);
+    return pass4 <= pass8;
+}
+
+// The configuration of the one-shot form launch_rowtile takes for a layer: waves per workgroup, output tiles per wave (the smallest of
+// {2,3,4} that covers NOUT in one pass of 8 waves; 4-wave workgroups for big batches) and k-steps of weight fragments resident in
+// registers (as many as ~128 VGPRs allow).  Rows that cannot be read 16 bytes at a time (width not a multiple of 8, unaligned base) take
+// the element-load instantiation.  ONE function for the launch and for the wide form's dispatch (rowtile_fwd_too_wide).
+struct RtShape { int nwv, ntw, ksmax; };
+static inline RtShape rowtile_shape(const RowTileParams& p, int ct_size, bool bwd) {
+    if (p.vec_in != 8 && p.vec_in != 4) return RtShape{8, 4, bwd ? 3 : 4};
+    const int n_tiles = ceil_div(p.NOUT, 16);
+    if (use_four_waves(p)) {                                  // 4 waves cover 8 / 12 / 16 column tiles per pass
+        if (n_tiles <= 4 * 2) return RtShape{4, 2, 12};
+        if (n_tiles <= 4 * 3) return RtShape{4, 3, 7};
+        if (n_tiles <= 4 * 4) return RtShape{4, 4, 5};
+        if (n_tiles > 20 && n_tiles <= 24) return RtShape{4, 6, 3};      // 360 columns in one pass
+        return RtShape{4, 5, 4};                                          // 300 / 600 columns: one / two passes of 20 tiles
+    }
+    if (n_tiles <= RT_WAVES * 2) {
+        // 13 k-steps = the C-GCN input width (2 x 200 BiLSTM states): one more resident k-step instead of a second load phase
+        if (p.Kpad / (ct_size == 2 ? 32 : 16) == 13) return RtShape{8, 2, 13};
+        return RtShape{8, 2, 12};
+    }
+    if (n_tiles <= RT_WAVES * 3) return RtShape{8, 3, 7};
+    return RtShape{8, 4, 5};
+}
+
+// LDS bytes a one-shot launch asks for: the S tile, the out tile (bwd: the larger of it and the Z tile), the tile's adjacency tables and
+// the bias of a column pass.  launch_rowtile_cfg refuses a launch above ROWTILE_LDS_MAX; the wide form (wide_kernels.hip) takes exactly
+// the forward launches it would refuse
+constexpr size_t ROWTILE_LDS_MAX = 160 * 1024;
+static inline size_t rowtile_lds_bytes(int Kpad, int NOUT, int ct_size, int ot_size, bool bwd, int nwv, int ntw) {
+    const int stride = lds_stride_dw(Kpad * ct_size / 4) * 4 / ct_size;
+    const int ncols_pass = nwv * ntw * 16;
+    const int ostride = out_stride_dw(std::min(round_up(NOUT, 16), ncols_pass) * ot_size / 4) * 4 / ot_size;
+    const size_t s_bytes = (size_t)ROWS * stride * ct_size, o_bytes = (size_t)ROWS * ostride * ot_size;
+    return s_bytes + (bwd ? std::max(s_bytes, o_bytes) : o_bytes) + (size_t)ROWS * 13 * sizeof(int) + (size_t)std::max(nwv * WAVE, ncols_pass) * sizeof(float);
+}
+// Whether the one-shot forward launch of p would be refused for its LDS (the column-split form, tried first, never takes such a layer:
+// its configurations hold at most 20 k-steps)
+static inline bool rowtile_fwd_too_wide(const RowTileParams& p, int ct_size, int ot_size) {
+    const RtShape sh = rowtile_shape(p, ct_size, false);
+    return rowtile_lds_bytes(p.Kpad, p.NOUT, ct_size, ot_size, false, sh.nwv, sh.ntw) > ROWTILE_LDS_MAX;
+}
+
+// the wide form of a forward layer launch (wide_kernels.hip): aggregate into the S fragment image p.frag_out, then transform it
+int wide_fwd_launch(hipStream_t s, const RowTileParams& p, int in_dtype, int out_dtype, int compute);
+
 // one precision combination x one direction of the row-tile kernel (rowtile_part.hip): combo 0 = exact f32; 1..4 = bf16 MFMA operands
 // with (in, out) activations (f32, f32), (f32, bf16), (bf16, f32), (bf16, bf16); mode 0 = forward, 1 = backward-data deriving dZ from
 // dY and Y, 2 = backward-data on ready-made dZ rows
@@ -352,13 +411,8 @@ int rowtile_launch(int combo, int mode, hipStream_t s, const RowTileParams& p);
 #ifdef GCNPT_RT_PART
 template <typename CT, typename IT, typename OT, bool BWD, int VEC, int NTW, int KSMAX, bool DZIN = false, int NWV = 8>
 static inline int launch_rowtile_cfg(hipStream_t s, const RowTileParams& p) {
-    const int stride = lds_stride_dw(p.Kpad * (int)sizeof(CT) / 4) * 4 / (int)sizeof(CT);
-    const int ncols_pass = NWV * NTW * 16;
-    const int ostride = out_stride_dw(std::min(round_up(p.NOUT, 16), ncols_pass) * (int)sizeof(OT) / 4) * 4 / (int)sizeof(OT);
-    const size_t s_bytes = (size_t)ROWS * stride * sizeof(CT), o_bytes = (size_t)ROWS * ostride * sizeof(OT);
-    const size_t lds = s_bytes + (BWD ? std::max(s_bytes, o_bytes) : o_bytes) +
-                       (size_t)ROWS * 13 * sizeof(int) + (size_t)std::max(NWV * WAVE, ncols_pass) * sizeof(float);
-    if (lds > 160 * 1024) return fail(GCNPT_E_UNSUPPORTED, "layer: K=%d needs %zu B of LDS per workgroup", p.K, lds);
+    const size_t lds = rowtile_lds_bytes(p.Kpad, p.NOUT, (int)sizeof(CT), (int)sizeof(OT), BWD, NWV, NTW);
+    if (lds > ROWTILE_LDS_MAX) return fail(GCNPT_E_UNSUPPORTED, "layer: K=%d needs %zu B of LDS per workgroup", p.K, lds);
     const int n_tiles = ceil_div(p.N, ROWS);
     // the uniform-precision instantiations can carry the layer above's weight gradient on the CUs that have no row tile
     if constexpr (NWV == 8 && BWD && DZIN && std::is_same<IT, OT>::value && sizeof(CT) == sizeof(IT)) {
@@ -382,48 +436,33 @@ static inline int launch_rowtile_cfg(hipStream_t s, const RowTileParams& p) {
     return GCNPT_OK;
 }
 
-// Big batches (more row tiles than CUs): workgroups of 4 waves, two or three per CU, so that one workgroup's memory waits overlap another's
-// arithmetic (the 8-wave form keeps ~240 registers per wave: one workgroup per CU, nothing to overlap with).  Measured (C2 widths,
-// B = 64 ... 1024; C5 widths): slower below ~256 tiles (B = 80: +20 %), 3 % faster at B = 100, 9-12 % faster from B = 256 on and at the
-// C5 shape; not when the narrower workgroup needs one more column pass than the wide one (360 columns: 23 tiles = 20 + 3).
-// gcnpt_set_option(GCNPT_OPT_FOUR_WAVES, 0 / 1) forces the choice (A/B, tests).
-static inline bool use_four_waves(const RowTileParams& p) {
-    const int forced = option(GCNPT_OPT_FOUR_WAVES);
-    if (forced == 0 || forced == 1) return forced == 1;
-    if (ceil_div(p.N, ROWS) <= 256) return false;
-    const int n_tiles = ceil_div(p.NOUT, 16);
-    const int pass8 = n_tiles <= 24 ? 1 : ceil_div(n_tiles, 32), pass4 = n_tiles <= 24 ? 1 : ceil_div(n_tiles, 20);
-    return pass4 <= pass8;
-}
-
 // the column-split form for small batches of wide layers (colsplit_body.h): GCNPT_OK / an error when it took the launch, GCNPT_NOT_TAKEN when it does not apply
 constexpr int GCNPT_NOT_TAKEN = 1;
 template <typename CT, typename IT, typename OT, bool BWD, int VEC, bool DZIN>
 static inline int try_colsplit(hipStream_t s, const RowTileParams& p);
 
-// output tiles per wave: the smallest of {2,3,4} that covers NOUT in one pass (8 waves x NTW x 16 columns),
-// with as many K-steps of weight fragments resident in registers as ~128 VGPRs allow.  Rows that cannot be
-// read 16 bytes at a time (width not a multiple of 8, unaligned base) take the element-load instantiation.
+// the one-shot configuration rowtile_shape picks, as the instantiation that runs it
 template <typename CT, typename IT, typename OT, bool BWD, int VEC, bool DZIN>
 static inline int launch_rowtile_vec(hipStream_t s, const RowTileParams& p) {
-    const int n_tiles = ceil_div(p.NOUT, 16);
     {
         const int rc = try_colsplit<CT, IT, OT, BWD, VEC, DZIN>(s, p);
         if (rc != GCNPT_NOT_TAKEN) return rc;
     }
-    if (use_four_waves(p)) {                                  // 4 waves cover 8 / 12 / 16 column tiles per pass
-        if (n_tiles <= 4 * 2) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 12, DZIN, 4>(s, p);
-        if (n_tiles <= 4 * 3) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 3, 7, DZIN, 4>(s, p);
-        if (n_tiles <= 4 * 4) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 4, 5, DZIN, 4>(s, p);
-        if (n_tiles > 20 && n_tiles <= 24) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 6, 3, DZIN, 4>(s, p);      // 360 columns in one pass
-        return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 5, 4, DZIN, 4>(s, p);      // 300 / 600 columns: one / two passes of 20 tiles
+    const RtShape sh = rowtile_shape(p, (int)sizeof(CT), BWD);
+    if (sh.nwv == 4) {
+        switch (sh.ntw) {
+            case 2: return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 12, DZIN, 4>(s, p);
+            case 3: return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 3, 7, DZIN, 4>(s, p);
+            case 4: return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 4, 5, DZIN, 4>(s, p);
+            case 6: return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 6, 3, DZIN, 4>(s, p);
+            default: return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 5, 4, DZIN, 4>(s, p);
+        }
     }
-    if (n_tiles <= RT_WAVES * 2) {
-        // 13 k-steps = the C-GCN input width (2 x 200 BiLSTM states): one more resident k-step instead of a second load phase
-        if (p.Kpad / (sizeof(CT) == 2 ? 32 : 16) == 13) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 13, DZIN>(s, p);
+    if (sh.ntw == 2) {
+        if (sh.ksmax == 13) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 13, DZIN>(s, p);
         return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 12, DZIN>(s, p);
     }
-    if (n_tiles <= RT_WAVES * 3) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 3, 7, DZIN>(s, p);
+    if (sh.ntw == 3) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 3, 7, DZIN>(s, p);
     return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 4, 5, DZIN>(s, p);
 }
 
@@ -431,7 +470,7 @@ template <typename CT, typename IT, typename OT, bool BWD, bool DZIN = false>
 static inline int launch_rowtile(hipStream_t s, const RowTileParams& p) {
     if (p.vec_in == 8) return launch_rowtile_vec<CT, IT, OT, BWD, 8, DZIN>(s, p);
     if (p.vec_in == 4) return launch_rowtile_vec<CT, IT, OT, BWD, 4, DZIN>(s, p);
-    return launch_rowtile_cfg<CT, IT, OT, BWD, 0, 4, BWD ? 3 : 4, DZIN>(s, p);
+    return launch_rowtile_cfg<CT, IT, OT, BWD, 0, 4, BWD ? 3 : 4, DZIN>(s, p);      // rowtile_shape: {8, 4, BWD ? 3 : 4}
 }
 
 #endif

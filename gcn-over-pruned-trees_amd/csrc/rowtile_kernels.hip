@@ -65,6 +65,37 @@ static int dispatch_rowtile(hipStream_t s, const RowTileParams& p, int in_dtype,
     return rowtile_launch(combo, mode, s, p);
 }
 
+// Whether a forward launch takes the wide form (wide_kernels.hip): GCNPT_OPT_WIDE_FORM = -1 where the one-shot row tile would be refused
+// for its LDS (rowtile_fwd_too_wide, the byte count launch_rowtile_cfg checks), 1 always, 0 never
+static bool take_wide_form(const RowTileParams& p, int compute_dtype, int out_dtype) {
+    const int forced = option(GCNPT_OPT_WIDE_FORM);
+    if (forced >= 0) return forced == 1;
+    return rowtile_fwd_too_wide(p, (int)esize(compute_dtype), (int)esize(out_dtype));
+}
+
+// The same decision for a layer of a stack, from its sizes and its input rows (which decide the row loads, hence the one-shot shape)
+static bool layer_takes_wide_form(int B, int T, int Din, int H, const void* h, int h_dtype, int out_dtype, int compute_dtype) {
+    if (B <= 0 || T < 0 || Din <= 0 || H <= 0 || !dtype_ok(h_dtype) || !dtype_ok(out_dtype) || !dtype_ok(compute_dtype)) return false;
+    RowTileParams p{};
+    p.N = (int)rows_of(B, T); p.K = Din; p.NOUT = H; p.Kpad = round_up(Din, kstep_of(compute_dtype));
+    p.vec_in = vec_elems(Din, esize(h_dtype), h, nullptr);
+    return take_wide_form(p, compute_dtype, out_dtype);
+}
+
+// A stack is checked as a whole before its first launch: a wide layer without its S image fails the call with nothing enqueued, not
+// after the layers below it (or the weight pack of gcnpt_layers_step) have run
+static int check_stack_s_frag(const char* what, int n_layers, const void* x, int x_dtype, void* const* out, const int* out_dtype, int B, int T,
+                              const int* Din, const int* H, int compute_dtype, void* const* s_frag) {
+    for (int l = 0; l < n_layers; ++l) {
+        const void* h = l == 0 ? x : out[l - 1];
+        const int h_dtype = l == 0 ? x_dtype : out_dtype[l - 1];
+        if (!(s_frag && s_frag[l]) && layer_takes_wide_form(B, T, Din[l], H[l], h, h_dtype, out_dtype[l], compute_dtype))
+            return fail(GCNPT_E_INVALID, "%s: layer %d (Din=%d, H=%d) takes the wide form, which stages S = (A+I)h through s_frag[%d]: pass "
+                        "gcnpt_frag_bytes(rows, Din, compute_dtype) bytes (gcnpt_layer_fwd_needs_s_frag says where)", what, l, Din[l], H[l], l);
+    }
+    return GCNPT_OK;
+}
+
 static int layer_fwd_impl(void* stream, const void* h, int h_dtype, const void* w_fwd, const float* bias,
                           const int32_t* row_ptr, const int32_t* col_idx, const int32_t* ell, const int32_t* deg_ell,
                           int B, int T, int Din, int H, void* out, int out_dtype, int compute_dtype, float drop_p,
@@ -85,7 +116,25 @@ static int layer_fwd_impl(void* stream, const void* h, int h_dtype, const void* 
     p.drop_p = drop_p; p.scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
     p.drop_thresh16 = (unsigned)((double)drop_p * 65536.0);
     p.seed = seed; p.seed_dev = seed_dev;
+    if (take_wide_form(p, compute_dtype, out_dtype)) return wide_fwd_launch((hipStream_t)stream, p, h_dtype, out_dtype, compute_dtype);
     return dispatch_rowtile<false>((hipStream_t)stream, p, h_dtype, out_dtype, compute_dtype);
+}
+
+// host-only: whether gcnpt_layer_fwd over N rows of Din columns may take the wide form, i.e. needs s_frag even without a backward pass.
+// It knows no pointers, so it answers for the widest case the call could be: a float32 output (the wider out tile) and rows either
+// 16-byte aligned or not (the element-load shape; its out tile and bias pass are never smaller than the vector shapes').  1 where any
+// of these takes the wide form: never 0 for a layer that then needs s_frag, at most a spare image near the limit.
+extern "C" int gcnpt_layer_fwd_needs_s_frag(int N, int Din, int H, int compute_dtype) {
+    GCNPT_REQUIRE(N > 0 && Din > 0 && H > 0 && dtype_ok(compute_dtype), "layer_fwd_needs_s_frag: bad argument (N=%d, Din=%d, H=%d, dtype %d)", N,
+                  Din, H, compute_dtype);
+    RowTileParams p{};
+    p.N = N; p.K = Din; p.NOUT = H; p.Kpad = round_up(Din, kstep_of(compute_dtype));
+    bool wide = false;
+    for (int vec : {0, Din % 8 == 0 ? 8 : (Din % 4 == 0 ? 4 : 0)}) {
+        p.vec_in = vec;
+        wide = wide || take_wide_form(p, compute_dtype, GCNPT_F32);
+    }
+    return wide ? 1 : 0;
 }
 
 extern "C" int gcnpt_layer_fwd(void* stream, const void* h, int h_dtype, const void* w_fwd, const float* bias,
@@ -215,6 +264,10 @@ extern "C" int gcnpt_layers_fwd(void* stream, int n_layers, const void* x, int x
     GCNPT_REQUIRE(x && w_fwd && bias && Din && H && out && out_dtype && drop_p && seed, "layers_fwd: null pointer");
     for (int l = 1; l < n_layers; ++l)
         GCNPT_REQUIRE(Din[l] == H[l - 1], "layers_fwd: layer %d reads %d columns but layer %d writes %d", l, Din[l], l - 1, H[l - 1]);
+    {
+        const int rc = check_stack_s_frag("layers_fwd", n_layers, x, x_dtype, out, out_dtype, B, T, Din, H, compute_dtype, s_frag);
+        if (rc != GCNPT_OK) return rc;
+    }
     const void* h = x;
     int h_dtype = x_dtype;
     for (int l = 0; l < n_layers; ++l) {
@@ -316,6 +369,11 @@ extern "C" int gcnpt_layers_step(void* stream, const gcnpt_step_t* st) {
     GCNPT_REQUIRE(st, "layers_step: null pointer");
     const int L = st->n_layers;
     GCNPT_REQUIRE(L >= 1 && L <= LAYERS_MAX, "layers_step: 1..%d layers per call", LAYERS_MAX);
+    if (st->parts & 2) {                         // before the weight pack is enqueued
+        const int rc = check_stack_s_frag("layers_step", L, st->x, st->x_dtype, st->out, st->out_dtype, st->B, st->T, st->Din, st->H,
+                                          st->compute_dtype, st->s_frag);
+        if (rc != GCNPT_OK) return rc;
+    }
     if (st->parts & 1) {
         const int rc = gcnpt_pack_weights_multi(stream, L, st->W, st->H, st->Din, st->compute_dtype, st->w_fwd, st->w_bwd);
         if (rc != GCNPT_OK) return rc;

@@ -106,16 +106,22 @@ template <typename IT, int NBU> struct GatherItem { raw8<IT> s, sy, nb[NBU], nby
 //        line and drop it.  MASKED: the loader derives dZ = dY * 1[Y>0] * scale / (deg+1) for the row and its neighbours;
 //   (2b) every other row is a plain copy (tile_copy_item).
 // VEC: 8 = rows read 16 bytes at a time (K % 8 == 0), 4 = in 8-byte (bf16) / 16-byte (f32) halves (K % 4 == 0), 0 = element loads.
-template <typename CT, typename IT, bool MASKED, int VEC, int NBU>
+// KCHUNK (the wide form's aggregate, wide_kernels.hip): the tile holds only the columns [kofs, kofs + 8 nck) of its rows.  Column numbers
+// k0 stay absolute, so p.K is still both the row stride and the valid width of every load; only the chunk count, its divisor and where a
+// chunk lands in S (column k0 - kofs) change.  Without it kbase() is the constant 0 and the code is the one-shot form's.
+template <typename CT, typename IT, bool MASKED, int VEC, int NBU, bool KCHUNK = false>
 struct TileGather {
     const RowTileParams& p;
     const TileMeta& m;
     CT* S;                      // the tile in LDS, `stride` CT elements per row
     int stride, r0;
+    int kofs = 0, nck = 0;      // KCHUNK: first column and 8-column chunks of the slice
+    unsigned cmagic = 0;        // KCHUNK: ceil(2^32 / nck)
 
-    __device__ __forceinline__ int nchunk() const { return p.Kpad / 8; }
+    __device__ __forceinline__ int nchunk() const { if constexpr (KCHUNK) return nck; else return p.Kpad / 8; }
+    __device__ __forceinline__ int kbase() const { if constexpr (KCHUNK) return kofs; else return 0; }
     __device__ __forceinline__ int kmax8() const { return VEC == 8 ? p.K - 8 : (VEC == 4 ? p.K - 4 : p.K - 1); }
-    __device__ __forceinline__ int div_chunk(int x) const { return (int)__umulhi((unsigned)x, p.chunk_magic); }    // x / nchunk, exact for x * nchunk < 2^32
+    __device__ __forceinline__ int div_chunk(int x) const { return (int)__umulhi((unsigned)x, KCHUNK ? cmagic : p.chunk_magic); }    // x / nchunk, exact for x * nchunk < 2^32
     __device__ __forceinline__ const IT* src() const { return static_cast<const IT*>(p.src); }
     __device__ __forceinline__ const IT* yref() const { return static_cast<const IT*>(p.yref); }
     __device__ __forceinline__ void ld8(const IT* base, size_t row, int k0c, raw8<IT>& dst) const {
@@ -125,7 +131,7 @@ struct TileGather {
     }
     // a chunk of one of the tile's own rows (item `it` of the row-major chunk order)
     __device__ __forceinline__ void issue_self(int it, raw8<IT>& s, raw8<IT>& sy) const {
-        const int row = div_chunk(it), k0 = (it - row * nchunk()) * 8;
+        const int row = div_chunk(it), k0 = (it - row * nchunk()) * 8 + kbase();
         const size_t r = (size_t)min(r0 + row, p.N - 1);
         ld8(src(), r, min(k0, kmax8()), s);
         if (MASKED) ld8(yref(), r, min(k0, kmax8()), sy);
@@ -134,7 +140,7 @@ struct TileGather {
         const bool has = gi < n_g;
         const int li = has ? div_chunk(gi) : 0;
         row = has ? m.glist[li] : 0;
-        k0 = has ? (gi - li * nchunk()) * 8 : 0;
+        k0 = has ? (gi - li * nchunk()) * 8 + kbase() : 0;
         n = (has && k0 < p.K) ? m.rell[row * 8] : 0;
         return has;
     }
@@ -242,17 +248,17 @@ struct TileGather {
         };
         for (int e0 = NBU; e0 < n_ell; e0 += NBU) round(e0, n_ell, std::true_type{});
         for (int e0 = NB_INLINE; e0 < n; e0 += NBU) round(e0, n, std::false_type{});
-        if (has) tile<CT>::put8(S + (size_t)row * stride + k0, acc);
+        if (has) tile<CT>::put8(S + (size_t)row * stride + (k0 - kbase()), acc);
     }
     // (2b) a chunk of the tile's own rows: into S unless the row aggregates (finish() writes those), into Z for the backward's image
     template <bool BWD>
     __device__ __forceinline__ void copy_item(int it, const raw8<IT>& s, const raw8<IT>& sy, CT* Z) const {
         if (it >= ROWS * nchunk()) return;
-        const int row = div_chunk(it), k0 = (it - row * nchunk()) * 8;
+        const int row = div_chunk(it), k0 = (it - row * nchunk()) * 8 + kbase(), kt = k0 - kbase();     // absolute / tile column
         const bool live = r0 + row < p.N && k0 < p.K;
         const bool to_s = !(p.out && m.rell[row * 8] > 0);
         if constexpr (!BWD && sizeof(IT) == 2 && sizeof(CT) == 2) {     // bf16 rows into a bf16 tile: the 16 bytes as they are
-            if (to_s) *reinterpret_cast<uint4*>(S + (size_t)row * stride + k0) = live ? s.a : make_uint4(0, 0, 0, 0);
+            if (to_s) *reinterpret_cast<uint4*>(S + (size_t)row * stride + kt) = live ? s.a : make_uint4(0, 0, 0, 0);
             return;
         }
         float acc[8];
@@ -265,9 +271,9 @@ struct TileGather {
             for (int j = 0; j < 8; ++j) acc[j] = (y[j] > 0.0f) ? acc[j] * inv : 0.0f;
         }
         if (BWD) {
-            if (p.frag_out) tile<CT>::put8(Z + (size_t)row * stride + k0, acc);
+            if (p.frag_out) tile<CT>::put8(Z + (size_t)row * stride + kt, acc);
         }
-        if (to_s) tile<CT>::put8(S + (size_t)row * stride + k0, acc);
+        if (to_s) tile<CT>::put8(S + (size_t)row * stride + kt, acc);
     }
 };
 

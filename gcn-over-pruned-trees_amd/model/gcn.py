@@ -134,7 +134,10 @@ class _GCNLayersFn(torch.autograd.Function):
         need_w = any(p.requires_grad for p in params)
         g_ell = trees.empty_ell() if cfg["no_adj"] else trees.ell
         outs = [torch.empty(lead + (H,), dtype=cfg["out_dtype"] if l == L - 1 else cfg["mid_dtype"], device=dev) for l, (H, _) in enumerate(dims)]
-        s_frag = [torch.empty((lib.gcnpt_frag_bytes(rows, K, compute),), **u8) if need_w else None for _, K in dims]
+        # the S images: for the weight gradients, and for every layer that takes the wide form (staged through its image even in
+        # a no-grad forward; gcnpt_layer_fwd_needs_s_frag answers on the host)
+        s_frag = [torch.empty((lib.gcnpt_frag_bytes(rows, K, compute),), **u8)
+                  if need_w or lib.gcnpt_layer_fwd_needs_s_frag(rows, K, H, compute) == 1 else None for H, K in dims]
         # every layer's launch from ONE native call (gcnpt_layers_fwd): no interpreter time between the launches
         _lib.check(lib.gcnpt_layers_fwd(
             st, L, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr_array(wf), _lib.ptr_array(b32), _lib.ptr(trees.row_ptr),
@@ -149,7 +152,7 @@ class _GCNLayersFn(torch.autograd.Function):
         ctx.param_dtypes = [p.dtype for p in params]
         pool = cfg.get("pool")
         if pool is None:
-            ctx.save_for_backward(*outs, *wb, *[f for f in s_frag if f is not None])
+            ctx.save_for_backward(*outs, *wb, *(s_frag if need_w else []))
             return outs[-1]
         # the consumer of the stack, fused into the op (gcn.py:114-121): the three masked poolings in one pass over h_L.  Its backward
         # then hands the top layer dZ instead of dh (gcnpt_pool3_bwd_dz), and that layer gathers one row per neighbour, not three
@@ -160,7 +163,7 @@ class _GCNLayersFn(torch.autograd.Function):
         argmax = torch.empty((B, 3, H), dtype=torch.int32, device=dev) if kind == 0 else None
         _lib.check(lib.gcnpt_pool3_fwd(st, _lib.ptr(outs[-1]), _lib.dtype_code(outs[-1].dtype), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op), B, T, H, kind,
                                        _lib.ptr(pooled), _lib.ptr(argmax)))
-        ctx.save_for_backward(*outs, *wb, *[f for f in s_frag if f is not None])
+        ctx.save_for_backward(*outs, *wb, *(s_frag if need_w else []))
         ctx.pool = (pm, sp, op, argmax, kind)
         return pooled
 

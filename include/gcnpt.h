@@ -78,12 +78,17 @@ const char* gcnpt_last_error(void);
  *   GCNPT_OPT_COL_SPLIT     (env GCNPT_COL_SPLIT, default -1 = by shape)  the column-split form of the layer kernel (bf16 MFMA operands): every
  *       32-row tile is given to 2 ... 8 workgroups that gather the same rows and each produce a share of the output columns, so that a
  *       small batch of a wide layer spreads the layer's weight fragments over the CUs that have no tile.  By itself: <= 128 row tiles and
- *       >= 170 KB of weight fragments.  0: never;  n >= 1: always, with at least n workgroups per tile (tests).  Same values bit for bit */
+ *       >= 170 KB of weight fragments.  0: never;  n >= 1: always, with at least n workgroups per tile (tests).  Same values bit for bit
+ *   GCNPT_OPT_WIDE_FORM     (env GCNPT_WIDE_FORM, default -1)  the wide form of the layer forward (two launches: aggregate S = (A+I) h into
+ *       the s_frag image, then transform it), for inputs whose 32-row tile does not fit the row-tile kernel's LDS (fp32: Din > 1024 at H = 200,
+ *       see gcnpt_layer_fwd).  -1: exactly where the row tile would be refused;  1: every forward layer launch (tests, A/B);  0: never (such
+ *       a layer returns GCNPT_E_UNSUPPORTED again).  Same values bit for bit wherever both forms run */
 #define GCNPT_OPT_DETERMINISTIC 0
 #define GCNPT_OPT_FOUR_WAVES 1
 #define GCNPT_OPT_SIDE_TILES 2
 #define GCNPT_OPT_COL_SPLIT 3
-#define GCNPT_OPT_COUNT 4
+#define GCNPT_OPT_WIDE_FORM 4
+#define GCNPT_OPT_COUNT 5
 int gcnpt_set_option(int option, int value);
 int gcnpt_get_option(int option);
 
@@ -197,7 +202,16 @@ size_t gcnpt_frag_bytes(int rows, int width, int dtype);
  * of S = (A+I) h for gcnpt_layer_bwd_weight.
  * seed_dev: NULL, or [dev] one uint64 that the kernel adds to `seed` when it runs: a counter the caller advances
  * between replays of a captured hipGraph, so that a replayed training step draws a new dropout mask (a by-value
- * seed is frozen into the graph). */
+ * seed is frozen into the graph).
+ * Width rule: the one-shot row-tile kernel keeps a 32-row tile of S next to its out tile in 160 KiB of LDS.  Where that does not
+ * fit (fp32 at H = 200: Din > 1024, 1 040 being the first multiple of 16 refused; bf16 operands hold about twice that) the call takes
+ * the WIDE FORM (GCNPT_OPT_WIDE_FORM): two launches that stage S through s_frag, which is then REQUIRED even for inference
+ * (GCNPT_E_INVALID when NULL, checked before any HIP call).  gcnpt_layer_fwd_needs_s_frag(N, Din, H, compute_dtype) answers on the
+ * host, without a GPU, whether a layer over N rows may take that form (1) or not (0), -1 for bad arguments; knowing no pointers it
+ * answers for the widest case (float32 output, rows of any alignment), so a 0 is never followed by a wide launch.  Every other shape
+ * launches what it launched before.  The same rule holds for gcnpt_layers_fwd and gcnpt_layers_step, layer by layer; they check every
+ * layer before their first launch (gcnpt_layers_step: before the weight pack), so a missing image leaves nothing enqueued. */
+int gcnpt_layer_fwd_needs_s_frag(int N, int Din, int H, int compute_dtype);
 int gcnpt_layer_fwd(void* stream, const void* h, int h_dtype, const void* w_fwd, const float* bias,
                     const int32_t* row_ptr, const int32_t* col_idx, const int32_t* ell, const int32_t* deg_ell, int B,
                     int T, int Din, int H, void* out, int out_dtype, int compute_dtype, float drop_p, uint64_t seed,
