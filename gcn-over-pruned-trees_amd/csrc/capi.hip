@@ -26,15 +26,18 @@ int fail(int code, const char* fmt, ...) {
 // at the top of a call; the environment is consulted exactly once, when the library is loaded, for the defaults.
 static std::atomic<int> g_options[GCNPT_OPT_COUNT];
 static const bool g_options_init = [] {
-    const int defaults[GCNPT_OPT_COUNT] = {0, -1, 192, -1, -1};
-    const char* names[GCNPT_OPT_COUNT] = {"GCNPT_DETERMINISTIC", "GCNPT_WAVES4", "GCNPT_SIDE_TILES", "GCNPT_COL_SPLIT", "GCNPT_WIDE_FORM"};
+    const int defaults[GCNPT_OPT_COUNT] = {0, -1, 192, -1, -1, 0, -1};
+    const char* names[GCNPT_OPT_COUNT] = {"GCNPT_DETERMINISTIC", "GCNPT_WAVES4", "GCNPT_SIDE_TILES", "GCNPT_COL_SPLIT", "GCNPT_WIDE_FORM", nullptr,
+                                          "GCNPT_WIDE_BWD"};
     for (int i = 0; i < GCNPT_OPT_COUNT; ++i) {
-        const char* e = getenv(names[i]);
+        const char* e = names[i] ? getenv(names[i]) : nullptr;
         g_options[i].store((e && e[0]) ? atoi(e) : defaults[i], std::memory_order_relaxed);
     }
     return true;
 }();
 int option(int key) { return g_options[key].load(std::memory_order_relaxed); }
+// key 5 is not assigned (include/gcnpt.h): rejected as unknown, as before GCNPT_OPT_WIDE_BWD took key 6
+static bool option_known(int key) { return key >= 0 && key < GCNPT_OPT_COUNT && key != 5; }
 
 // shape of the calling thread's most recent layer-path launch (gcnpt_last_launch: what bench.py's launch-floor leg mirrors)
 static thread_local int t_last_launch[4] = {0, 0, 0, 0};
@@ -70,17 +73,18 @@ extern "C" int gcnpt_abi_version(void) { return GCNPT_ABI_VERSION; }
 extern "C" const char* gcnpt_last_error(void) { return gcnpt::err_buf(); }
 
 extern "C" int gcnpt_set_option(int option, int value) {
-    if (option < 0 || option >= GCNPT_OPT_COUNT) return gcnpt::fail(GCNPT_E_INVALID, "set_option: unknown option %d", option);
+    if (!gcnpt::option_known(option)) return gcnpt::fail(GCNPT_E_INVALID, "set_option: unknown option %d", option);
     if (option == GCNPT_OPT_DETERMINISTIC && value != 0 && value != 1) return gcnpt::fail(GCNPT_E_INVALID, "set_option: deterministic is 0 or 1");
     if (option == GCNPT_OPT_FOUR_WAVES && (value < -1 || value > 1)) return gcnpt::fail(GCNPT_E_INVALID, "set_option: four_waves is -1 (auto), 0 or 1");
     if (option == GCNPT_OPT_SIDE_TILES && value < 0) return gcnpt::fail(GCNPT_E_INVALID, "set_option: side_tiles must be >= 0");
     if (option == GCNPT_OPT_COL_SPLIT && (value < -1 || value > 8)) return gcnpt::fail(GCNPT_E_INVALID, "set_option: col_split is -1 (auto), 0 or 1..8 workgroups per row tile");
     if (option == GCNPT_OPT_WIDE_FORM && (value < -1 || value > 1)) return gcnpt::fail(GCNPT_E_INVALID, "set_option: wide_form is -1 (where the row tile cannot hold the tile), 0 or 1");
+    if (option == GCNPT_OPT_WIDE_BWD && (value < -1 || value > 1)) return gcnpt::fail(GCNPT_E_INVALID, "set_option: wide_bwd is -1 (where the row tile cannot hold the tiles), 0 or 1");
     gcnpt::g_options[option].store(value, std::memory_order_relaxed);
     return GCNPT_OK;
 }
 extern "C" int gcnpt_get_option(int option) {
-    if (option < 0 || option >= GCNPT_OPT_COUNT) return gcnpt::fail(GCNPT_E_INVALID, "get_option: unknown option %d", option);
+    if (!gcnpt::option_known(option)) return gcnpt::fail(GCNPT_E_INVALID, "get_option: unknown option %d", option);
     return gcnpt::option(option);
 }
 

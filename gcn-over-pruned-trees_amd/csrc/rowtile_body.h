@@ -383,8 +383,8 @@ static inline RtShape rowtile_shape(const RowTileParams& p, int ct_size, bool bw
 }
 
 // LDS bytes a one-shot launch asks for: the S tile, the out tile (bwd: the larger of it and the Z tile), the tile's adjacency tables and
-// the bias of a column pass.  launch_rowtile_cfg refuses a launch above ROWTILE_LDS_MAX; the wide form (wide_kernels.hip) takes exactly
-// the forward launches it would refuse
+// the bias of a column pass.  launch_rowtile_cfg refuses a launch above ROWTILE_LDS_MAX; the wide forms (wide_kernels.hip) take exactly
+// the forward and backward-data launches it would refuse
 constexpr size_t ROWTILE_LDS_MAX = 160 * 1024;
 static inline size_t rowtile_lds_bytes(int Kpad, int NOUT, int ct_size, int ot_size, bool bwd, int nwv, int ntw) {
     const int stride = lds_stride_dw(Kpad * ct_size / 4) * 4 / ct_size;
@@ -400,8 +400,17 @@ static inline bool rowtile_fwd_too_wide(const RowTileParams& p, int ct_size, int
     return rowtile_lds_bytes(p.Kpad, p.NOUT, ct_size, ot_size, false, sh.nwv, sh.ntw) > ROWTILE_LDS_MAX;
 }
 
+// Whether the one-shot backward-data launch of p would be refused for its LDS: two tiles of width H (the gathered one and the Z / out
+// tile).  The same shape and byte count launch_rowtile_cfg checks (the column-split form, tried first, never takes such a layer either)
+static inline bool rowtile_bwd_too_wide(const RowTileParams& p, int ct_size, int ot_size) {
+    const RtShape sh = rowtile_shape(p, ct_size, true);
+    return rowtile_lds_bytes(p.Kpad, p.NOUT, ct_size, ot_size, true, sh.nwv, sh.ntw) > ROWTILE_LDS_MAX;
+}
+
 // the wide form of a forward layer launch (wide_kernels.hip): aggregate into the S fragment image p.frag_out, then transform it
 int wide_fwd_launch(hipStream_t s, const RowTileParams& p, int in_dtype, int out_dtype, int compute);
+// the wide form of a backward-data launch (wide_kernels.hip): one launch, G = (A+I)^T dZ gathered chunk by chunk; dzin: src holds dZ
+int wide_bwd_launch(hipStream_t s, const RowTileParams& p, int in_dtype, int out_dtype, int compute, bool dzin);
 
 // one precision combination x one direction of the row-tile kernel (rowtile_part.hip): combo 0 = exact f32; 1..4 = bf16 MFMA operands
 // with (in, out) activations (f32, f32), (f32, bf16), (bf16, f32), (bf16, bf16); mode 0 = forward, 1 = backward-data deriving dZ from

@@ -73,6 +73,14 @@ static bool take_wide_form(const RowTileParams& p, int compute_dtype, int out_dt
     return rowtile_fwd_too_wide(p, (int)esize(compute_dtype), (int)esize(out_dtype));
 }
 
+// Whether a backward-data launch takes the wide form (wide_kernels.hip): GCNPT_OPT_WIDE_BWD = -1 where the one-shot row tile would be
+// refused for its LDS (rowtile_bwd_too_wide), 1 always, 0 never.  GCNPT_OPT_WIDE_FORM does not reach the backward
+static bool take_wide_bwd(const RowTileParams& p, int compute_dtype, int dh_dtype) {
+    const int forced = option(GCNPT_OPT_WIDE_BWD);
+    if (forced >= 0) return forced == 1;
+    return rowtile_bwd_too_wide(p, (int)esize(compute_dtype), (int)esize(dh_dtype));
+}
+
 // The same decision for a layer of a stack, from its sizes and its input rows (which decide the row loads, hence the one-shot shape)
 static bool layer_takes_wide_form(int B, int T, int Din, int H, const void* h, int h_dtype, int out_dtype, int compute_dtype) {
     if (B <= 0 || T < 0 || Din <= 0 || H <= 0 || !dtype_ok(h_dtype) || !dtype_ok(out_dtype) || !dtype_ok(compute_dtype)) return false;
@@ -170,6 +178,7 @@ static int layer_bwd_data_impl(void* stream, const void* dY, const void* Y, int 
     p.vec_out = dh ? vec_bytes(Din, esize(dh_dtype), dh, relu_src) : 0;
     p.scale = scale; p.drop_p = 0.0f;
     p.relu_src = relu_src; p.next_scale = next_scale;
+    if (take_wide_bwd(p, compute_dtype, dh_dtype)) return wide_bwd_launch((hipStream_t)stream, p, g_dtype, dh_dtype, compute_dtype, src_is_dz != 0);
     if (src_is_dz) return dispatch_rowtile<true, true>((hipStream_t)stream, p, g_dtype, dh_dtype, compute_dtype);
     return dispatch_rowtile<true>((hipStream_t)stream, p, g_dtype, dh_dtype, compute_dtype);
 }
@@ -198,11 +207,17 @@ static bool plan_side_wgrad(SideWgrads& sw, const WgradReq& r, int B, int T, int
 
 // Whether the backward-data launch of a layer carries `ride` (the layer above's weight gradient): what launch_rowtile_cfg / try_colsplit
 // decide when the launch is issued, as ONE predicate for the sweep's bookkeeping of launches it does not issue (gcnpt_layers_bwd_range):
-// the 8-wave one-shot form on ready-made dZ rows in uniform precision carries it, the 4-wave and the column-split forms never do.
+// the 8-wave one-shot form on ready-made dZ rows in uniform precision carries it, the 4-wave, column-split and wide forms never do.
 static bool would_carry(const void* g, const void* Y, int g_dtype, const void* dh, int dh_dtype, int compute_dtype, bool handed, int B, int T,
                         int H, int Din, const WgradReq& ride) {
     if (!handed || g_dtype != dh_dtype || esize(g_dtype) != esize(compute_dtype) || option(GCNPT_OPT_FOUR_WAVES) == 1) return false;
     const int N = (int)rows_of(B, T), Kpad = round_up(H, kstep_of(compute_dtype));
+    {
+        RowTileParams p{};                      // the launch layer_bwd_data_impl would issue: the wide form carries nothing
+        p.N = N; p.K = H; p.NOUT = Din; p.Kpad = Kpad;
+        p.vec_in = vec_elems(H, esize(g_dtype), g, Y);
+        if (take_wide_bwd(p, compute_dtype, dh_dtype)) return false;
+    }
     int split = 0;
     if (colsplit_plan(N, Kpad, Din, (int)esize(compute_dtype), vec_elems(H, esize(g_dtype), g, Y), false, dh != nullptr, &split) >= 0) return false;
     SideWgrads sw;
@@ -229,6 +244,7 @@ static int bwd_data_with_rider(void* stream, const void* dY, const void* Y, int 
                                float next_scale, int src_is_dz, const WgradReq* ride, bool launch_behind, bool* carried_out) {
     SideWgrads sw;
     t_side = SideWgrad{};
+    // (a launch that takes the wide form never reads t_side: carried stays false, and the gradient goes behind it or to the caller)
     if (ride && plan_side_wgrad(sw, *ride, B, T, compute_dtype)) t_side.sw = &sw;
     const int rc = layer_bwd_data_impl(stream, dY, Y, g_dtype, w_bwd, ell, rowT_ptr, colT_idx, ellT, B, T, Din, H, dh, dh_dtype, compute_dtype, scale,
                                        z_frag, zero_dW, zero_db, relu_src, next_scale, src_is_dz);

@@ -13,19 +13,9 @@
 // Both operands of the transform are in fragment order already: every global load is a lane-linear 16-byte load.  A 4-wave workgroup
 // owns 128 output columns, so it streams half of the weight image of a 200-column layer (555 KB in fp32 at Din = 1084) and a 32 x Din
 // slice of the S image (139 KB) through its CU.
-#include "rowtile_body.h"
+#include "wide_common.h"
 
 namespace gcnpt {
-
-constexpr int WIDE_THREADS = 256;                       // 4 waves
-constexpr int WIDE_WAVES = WIDE_THREADS / WAVE;
-constexpr int WIDE_KCHUNK = 256;                        // columns of S per chunk, a multiple of both k-steps: 33 KB of fp32 tile in LDS
-constexpr int WIDE_NTW = 2;                             // transform: output column tiles per wave
-constexpr int WIDE_COLS = WIDE_WAVES * WIDE_NTW * 16;   // transform: output columns per workgroup
-constexpr int WIDE_KB = 8;                              // transform: k-steps of weight fragments per register block (two in flight)
-
-// S chunk row stride in CT elements (the row tile's bank-spreading rule)
-__host__ __device__ inline int wide_s_stride(int ct_size) { return lds_stride_dw(WIDE_KCHUNK * ct_size / 4) * 4 / ct_size; }
 
 template <typename CT, typename IT, int VEC>
 __global__ __launch_bounds__(WIDE_THREADS) void wide_aggregate_kernel(const RowTileParams p) {

@@ -82,13 +82,21 @@ const char* gcnpt_last_error(void);
  *   GCNPT_OPT_WIDE_FORM     (env GCNPT_WIDE_FORM, default -1)  the wide form of the layer forward (two launches: aggregate S = (A+I) h into
  *       the s_frag image, then transform it), for inputs whose 32-row tile does not fit the row-tile kernel's LDS (fp32: Din > 1024 at H = 200,
  *       see gcnpt_layer_fwd).  -1: exactly where the row tile would be refused;  1: every forward layer launch (tests, A/B);  0: never (such
- *       a layer returns GCNPT_E_UNSUPPORTED again).  Same values bit for bit wherever both forms run */
+ *       a layer returns GCNPT_E_UNSUPPORTED again).  Same values bit for bit wherever both forms run.  It does not reach the backward
+ *   GCNPT_OPT_WIDE_BWD      (env GCNPT_WIDE_BWD, default -1)  the wide form of the layer backward-data (one launch: the workgroups of a row
+ *       tile each gather G = (A+I)^T dZ chunk by chunk and contract it against their share of the output columns, no workspace), for layers
+ *       whose two H-wide tiles do not fit the row-tile kernel's LDS (fp32: H > 608, bf16: H > 1216, see gcnpt_layer_bwd_data).  -1: exactly
+ *       where the row tile would be refused;  1: every backward-data launch (tests, A/B);  0: never (such a layer returns
+ *       GCNPT_E_UNSUPPORTED again).  Same dh / dZ hand-over and dZ image bit for bit wherever both forms run; a launch in the wide form never
+ *       carries the layer above's weight gradient (gcnpt_layers_bwd launches it at the end of the sweep)
+ * Key 5 is not assigned: gcnpt_set_option / gcnpt_get_option reject it as an unknown key, as they did before key 6 was added. */
 #define GCNPT_OPT_DETERMINISTIC 0
 #define GCNPT_OPT_FOUR_WAVES 1
 #define GCNPT_OPT_SIDE_TILES 2
 #define GCNPT_OPT_COL_SPLIT 3
 #define GCNPT_OPT_WIDE_FORM 4
-#define GCNPT_OPT_COUNT 5
+#define GCNPT_OPT_WIDE_BWD 6
+#define GCNPT_OPT_COUNT 7
 int gcnpt_set_option(int option, int value);
 int gcnpt_get_option(int option);
 

@@ -2,10 +2,13 @@
 """
 The GCN stack of the BERT no-RNN model (reference train.py:105,143-144: emb_dim = 1024; model/gcn.py:136,235-236: BERT-large vectors
 + POS + NER straight into the GCN), B = 50, T = 100, 1084 -> 200 -> 200, one fwd+bwd per step through gcn_layers: in fp32 the first
-layer takes the wide form (csrc/wide_kernels.hip).  As the yardstick, the same forward (and fwd+bwd) written the reference's way in
+layer takes the wide form (csrc/wide_kernels.hip).  --din / --hidden set other widths: e.g. --din 360 --hidden 768 (word ids + POS + NER
+into a GCN as wide as a BERT-base vector) or --din 1084 --hidden 1024, where fp32 backward-data takes its wide form in both layers
+(csrc/wide_bwd_kernels.hip).  As the yardstick, the same forward (and fwd+bwd) written the reference's way in
 torch on the same GPU: dense adj.bmm + nn.Linear per layer (gcn.py:269-271, 390-392).  Prints one JSON object; run it under
 `rocprofv3 --kernel-trace --stats -- python tools/bert_step.py` for the per-kernel times.
 """
+import argparse
 import json
 import os
 import sys
@@ -31,9 +34,9 @@ def timed(fn, steps, warmup):
     return 1000.0 * t0.elapsed_time(t1) / steps          # us per step
 
 
-def main(steps=50, warmup=10):
+def main(steps=50, warmup=10, din=1084, hidden=200):
     dev = torch.device("cuda:0")
-    B, T, dims, K = 50, 100, [1084, 200, 200], 1
+    B, T, dims, K = 50, 100, [din, hidden, hidden], 1
     tb = synthetic.random_tree_batch(1236, B, T, "tacred")
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
     trees = tree.prune_to_csr(t(tb["head"]), t(tb["subj_pos"]), t(tb["obj_pos"]), t(tb["deprel"]), K, masks=t(tb["masks"]))
@@ -79,4 +82,10 @@ def main(steps=50, warmup=10):
 
 
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser(description=__doc__.strip().splitlines()[0])
+    ap.add_argument("--din", type=int, default=1084, help="input columns of the first layer")
+    ap.add_argument("--hidden", type=int, default=200, help="hidden width of both layers")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    a = ap.parse_args()
+    main(a.steps, a.warmup, a.din, a.hidden)
