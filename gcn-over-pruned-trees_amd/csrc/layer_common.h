@@ -220,5 +220,12 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 static inline int kstep_of(int dtype) { return dtype == GCNPT_BF16 ? 32 : 16; }
 static inline size_t esize(int dtype) { return dtype == GCNPT_BF16 ? 2 : 4; }
 static inline bool dtype_ok(int d) { return d == GCNPT_F32 || d == GCNPT_BF16; }
+// the precision combination of a layer launch: 0 = exact f32; 1..4 = bf16 MFMA operands with (in, out) activations (f32, f32),
+// (f32, bf16), (bf16, f32), (bf16, bf16).  f32 compute on bf16 activations is refused (GCNPT_E_UNSUPPORTED, returned)
+static inline int precision_combo(int compute, int in_dtype, int out_dtype) {
+    if (compute == GCNPT_F32)
+        return in_dtype == GCNPT_F32 && out_dtype == GCNPT_F32 ? 0 : fail(GCNPT_E_UNSUPPORTED, "compute_dtype f32 needs f32 activations");
+    return in_dtype == GCNPT_F32 ? (out_dtype == GCNPT_F32 ? 1 : 2) : (out_dtype == GCNPT_F32 ? 3 : 4);
+}
 
 }  // namespace gcnpt

@@ -55,14 +55,49 @@ static int vec_bytes(int width, size_t es, const void* a, const void* b) {
 
 template <bool BWD, bool DZIN = false>
 static int dispatch_rowtile(hipStream_t s, const RowTileParams& p, int in_dtype, int out_dtype, int compute) {
-    const int mode = BWD ? (DZIN ? 2 : 1) : 0;
-    if (compute == GCNPT_F32) {
-        if (in_dtype != GCNPT_F32 || out_dtype != GCNPT_F32)
-            return fail(GCNPT_E_UNSUPPORTED, "compute_dtype f32 needs f32 activations");
-        return rowtile_launch(0, mode, s, p);
-    }
-    const int combo = in_dtype == GCNPT_F32 ? (out_dtype == GCNPT_F32 ? 1 : 2) : (out_dtype == GCNPT_F32 ? 3 : 4);
-    return rowtile_launch(combo, mode, s, p);
+    const int combo = precision_combo(compute, in_dtype, out_dtype);
+    return combo < 0 ? combo : rowtile_launch(combo, BWD ? (DZIN ? 2 : 1) : 0, s, p);
+}
+
+// The launch parameters of a forward layer over B x T rows, ONE builder for the launch (layer_fwd_impl) and for the predictions of
+// which form it takes (layer_takes_wide_form, gcnpt_layer_fwd_needs_s_frag).  No validation: pointers may be null
+static RowTileParams fwd_params(const void* h, int h_dtype, const void* w_fwd, const float* bias, const int32_t* row_ptr, const int32_t* col_idx,
+                                const int32_t* ell, const int32_t* deg_ell, int B, int T, int Din, int H, void* out, int out_dtype,
+                                int compute_dtype, float drop_p, uint64_t seed, void* s_frag, const uint64_t* seed_dev) {
+    RowTileParams p{};
+    p.stamps = static_cast<unsigned long long*>(g_debug_stamps); p.knob = g_debug_knob;
+    p.src = h; p.yref = nullptr; p.wfrag = w_fwd; p.bias = bias;
+    p.g_row_ptr = row_ptr; p.g_col_idx = col_idx; p.g_ell = ell; p.d_ell = deg_ell ? deg_ell : ell; p.out = out;
+    p.frag_out = s_frag;
+    p.N = (int)rows_of(B, T); p.T = T; p.K = Din; p.NOUT = H; p.Kpad = round_up(Din, kstep_of(compute_dtype));
+    p.chunk_magic = 0xffffffffu / (unsigned)std::max(p.Kpad / 8, 1) + 1u;
+    p.vec_in = vec_elems(Din, esize(h_dtype), h, nullptr);
+    p.vec_out = vec_bytes(H, esize(out_dtype), out, nullptr);
+    p.drop_p = drop_p; p.scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    p.drop_thresh16 = (unsigned)((double)drop_p * 65536.0);
+    p.seed = seed; p.seed_dev = seed_dev;
+    return p;
+}
+
+// The launch parameters of a backward-data layer over B x T rows, ONE builder for the launch (layer_bwd_data_impl) and for the sweep's
+// prediction of whether it carries a weight gradient (would_carry).  No validation: pointers may be null
+static RowTileParams bwd_params(const void* dY, const void* Y, int g_dtype, const void* w_bwd, const int32_t* ell, const int32_t* rowT_ptr,
+                                const int32_t* colT_idx, const int32_t* ellT, int B, int T, int Din, int H, void* dh, int dh_dtype,
+                                int compute_dtype, float scale, void* z_frag, float* zero_dW, float* zero_db, const void* relu_src,
+                                float next_scale, int src_is_dz) {
+    RowTileParams p{};
+    p.stamps = static_cast<unsigned long long*>(g_debug_stamps); p.knob = g_debug_knob;
+    p.src = dY; p.yref = Y; p.wfrag = w_bwd; p.bias = nullptr;
+    p.g_row_ptr = rowT_ptr; p.g_col_idx = colT_idx; p.g_ell = ellT; p.d_ell = ell; p.out = dh;
+    p.frag_out = z_frag;
+    p.zero_p[0] = zero_dW; p.zero_n[0] = H * Din; p.zero_p[1] = zero_db; p.zero_n[1] = H;
+    p.N = (int)rows_of(B, T); p.T = T; p.K = H; p.NOUT = Din; p.Kpad = round_up(H, kstep_of(compute_dtype));
+    p.chunk_magic = 0xffffffffu / (unsigned)std::max(p.Kpad / 8, 1) + 1u;
+    p.vec_in = vec_elems(H, esize(g_dtype), dY, src_is_dz ? nullptr : Y);
+    p.vec_out = dh ? vec_bytes(Din, esize(dh_dtype), dh, relu_src) : 0;
+    p.scale = scale; p.drop_p = 0.0f;
+    p.relu_src = relu_src; p.next_scale = next_scale;
+    return p;
 }
 
 // Whether a forward launch takes the wide form (wide_kernels.hip): GCNPT_OPT_WIDE_FORM = -1 where the one-shot row tile would be refused
@@ -84,9 +119,8 @@ static bool take_wide_bwd(const RowTileParams& p, int compute_dtype, int dh_dtyp
 // The same decision for a layer of a stack, from its sizes and its input rows (which decide the row loads, hence the one-shot shape)
 static bool layer_takes_wide_form(int B, int T, int Din, int H, const void* h, int h_dtype, int out_dtype, int compute_dtype) {
     if (B <= 0 || T < 0 || Din <= 0 || H <= 0 || !dtype_ok(h_dtype) || !dtype_ok(out_dtype) || !dtype_ok(compute_dtype)) return false;
-    RowTileParams p{};
-    p.N = (int)rows_of(B, T); p.K = Din; p.NOUT = H; p.Kpad = round_up(Din, kstep_of(compute_dtype));
-    p.vec_in = vec_elems(Din, esize(h_dtype), h, nullptr);
+    const RowTileParams p = fwd_params(h, h_dtype, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, Din, H, nullptr, out_dtype,
+                                       compute_dtype, 0.0f, 0, nullptr, nullptr);
     return take_wide_form(p, compute_dtype, out_dtype);
 }
 
@@ -113,17 +147,8 @@ static int layer_fwd_impl(void* stream, const void* h, int h_dtype, const void* 
     GCNPT_REQUIRE(dtype_ok(h_dtype) && dtype_ok(out_dtype) && dtype_ok(compute_dtype), "layer_fwd: bad dtype");
     GCNPT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f, "layer_fwd: drop_p=%f outside [0,1)", (double)drop_p);
     if (rows_of(B, T) > 0x7fffffffLL / 2) return fail(GCNPT_E_UNSUPPORTED, "layer_fwd: B*T too large");
-    RowTileParams p{};
-    p.stamps = static_cast<unsigned long long*>(g_debug_stamps); p.knob = g_debug_knob;
-    p.src = h; p.yref = nullptr; p.wfrag = w_fwd; p.bias = bias;
-    p.g_row_ptr = row_ptr; p.g_col_idx = col_idx; p.g_ell = ell; p.d_ell = deg_ell ? deg_ell : ell; p.out = out;
-    p.frag_out = s_frag;
-    p.N = (int)rows_of(B, T); p.T = T; p.K = Din; p.NOUT = H; p.Kpad = round_up(Din, kstep_of(compute_dtype)); p.chunk_magic = 0xffffffffu / (unsigned)(p.Kpad / 8) + 1u;
-    p.vec_in = vec_elems(Din, esize(h_dtype), h, nullptr);
-    p.vec_out = vec_bytes(H, esize(out_dtype), out, nullptr);
-    p.drop_p = drop_p; p.scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    p.drop_thresh16 = (unsigned)((double)drop_p * 65536.0);
-    p.seed = seed; p.seed_dev = seed_dev;
+    const RowTileParams p = fwd_params(h, h_dtype, w_fwd, bias, row_ptr, col_idx, ell, deg_ell, B, T, Din, H, out, out_dtype, compute_dtype, drop_p,
+                                       seed, s_frag, seed_dev);
     if (take_wide_form(p, compute_dtype, out_dtype)) return wide_fwd_launch((hipStream_t)stream, p, h_dtype, out_dtype, compute_dtype);
     return dispatch_rowtile<false>((hipStream_t)stream, p, h_dtype, out_dtype, compute_dtype);
 }
@@ -135,8 +160,9 @@ static int layer_fwd_impl(void* stream, const void* h, int h_dtype, const void* 
 extern "C" int gcnpt_layer_fwd_needs_s_frag(int N, int Din, int H, int compute_dtype) {
     GCNPT_REQUIRE(N > 0 && Din > 0 && H > 0 && dtype_ok(compute_dtype), "layer_fwd_needs_s_frag: bad argument (N=%d, Din=%d, H=%d, dtype %d)", N,
                   Din, H, compute_dtype);
-    RowTileParams p{};
-    p.N = N; p.K = Din; p.NOUT = H; p.Kpad = round_up(Din, kstep_of(compute_dtype));
+    // N rows: B = N token-packed rows (T = 0)
+    RowTileParams p = fwd_params(nullptr, GCNPT_F32, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, 0, Din, H, nullptr, GCNPT_F32,
+                                 compute_dtype, 0.0f, 0, nullptr, nullptr);
     bool wide = false;
     for (int vec : {0, Din % 8 == 0 ? 8 : (Din % 4 == 0 ? 4 : 0)}) {
         p.vec_in = vec;
@@ -167,17 +193,8 @@ static int layer_bwd_data_impl(void* stream, const void* dY, const void* Y, int 
     GCNPT_REQUIRE(B > 0 && T >= 0 && Din > 0 && H > 0, "layer_bwd_data: sizes must be positive");
     GCNPT_REQUIRE(dtype_ok(g_dtype) && dtype_ok(dh_dtype) && dtype_ok(compute_dtype), "layer_bwd_data: bad dtype");
     if (rows_of(B, T) > 0x7fffffffLL / 2) return fail(GCNPT_E_UNSUPPORTED, "layer_bwd_data: B*T too large");
-    RowTileParams p{};
-    p.stamps = static_cast<unsigned long long*>(g_debug_stamps); p.knob = g_debug_knob;
-    p.src = dY; p.yref = Y; p.wfrag = w_bwd; p.bias = nullptr;
-    p.g_row_ptr = rowT_ptr; p.g_col_idx = colT_idx; p.g_ell = ellT; p.d_ell = ell; p.out = dh;
-    p.frag_out = z_frag;
-    p.zero_p[0] = zero_dW; p.zero_n[0] = H * Din; p.zero_p[1] = zero_db; p.zero_n[1] = H;
-    p.N = (int)rows_of(B, T); p.T = T; p.K = H; p.NOUT = Din; p.Kpad = round_up(H, kstep_of(compute_dtype)); p.chunk_magic = 0xffffffffu / (unsigned)(p.Kpad / 8) + 1u;
-    p.vec_in = vec_elems(H, esize(g_dtype), dY, src_is_dz ? nullptr : Y);
-    p.vec_out = dh ? vec_bytes(Din, esize(dh_dtype), dh, relu_src) : 0;
-    p.scale = scale; p.drop_p = 0.0f;
-    p.relu_src = relu_src; p.next_scale = next_scale;
+    const RowTileParams p = bwd_params(dY, Y, g_dtype, w_bwd, ell, rowT_ptr, colT_idx, ellT, B, T, Din, H, dh, dh_dtype, compute_dtype, scale, z_frag,
+                                       zero_dW, zero_db, relu_src, next_scale, src_is_dz);
     if (take_wide_bwd(p, compute_dtype, dh_dtype)) return wide_bwd_launch((hipStream_t)stream, p, g_dtype, dh_dtype, compute_dtype, src_is_dz != 0);
     if (src_is_dz) return dispatch_rowtile<true, true>((hipStream_t)stream, p, g_dtype, dh_dtype, compute_dtype);
     return dispatch_rowtile<true>((hipStream_t)stream, p, g_dtype, dh_dtype, compute_dtype);
@@ -208,18 +225,15 @@ static bool plan_side_wgrad(SideWgrads& sw, const WgradReq& r, int B, int T, int
 // Whether the backward-data launch of a layer carries `ride` (the layer above's weight gradient): what launch_rowtile_cfg / try_colsplit
 // decide when the launch is issued, as ONE predicate for the sweep's bookkeeping of launches it does not issue (gcnpt_layers_bwd_range):
 // the 8-wave one-shot form on ready-made dZ rows in uniform precision carries it, the 4-wave, column-split and wide forms never do.
-static bool would_carry(const void* g, const void* Y, int g_dtype, const void* dh, int dh_dtype, int compute_dtype, bool handed, int B, int T,
+static bool would_carry(const void* g, const void* Y, int g_dtype, void* dh, int dh_dtype, int compute_dtype, bool handed, int B, int T,
                         int H, int Din, const WgradReq& ride) {
     if (!handed || g_dtype != dh_dtype || esize(g_dtype) != esize(compute_dtype) || option(GCNPT_OPT_FOUR_WAVES) == 1) return false;
-    const int N = (int)rows_of(B, T), Kpad = round_up(H, kstep_of(compute_dtype));
-    {
-        RowTileParams p{};                      // the launch layer_bwd_data_impl would issue: the wide form carries nothing
-        p.N = N; p.K = H; p.NOUT = Din; p.Kpad = Kpad;
-        p.vec_in = vec_elems(H, esize(g_dtype), g, Y);
-        if (take_wide_bwd(p, compute_dtype, dh_dtype)) return false;
-    }
+    // the launch layer_bwd_data_impl would issue (handed: on ready-made dZ rows, Y unread): the wide form carries nothing
+    const RowTileParams p = bwd_params(g, Y, g_dtype, nullptr, nullptr, nullptr, nullptr, nullptr, B, T, Din, H, dh, dh_dtype,
+                                       compute_dtype, 1.0f, nullptr, nullptr, nullptr, nullptr, 1.0f, 1);
+    if (take_wide_bwd(p, compute_dtype, dh_dtype)) return false;
     int split = 0;
-    if (colsplit_plan(N, Kpad, Din, (int)esize(compute_dtype), vec_elems(H, esize(g_dtype), g, Y), false, dh != nullptr, &split) >= 0) return false;
+    if (colsplit_plan(p.N, p.Kpad, p.NOUT, (int)esize(compute_dtype), p.vec_in, false, p.out != nullptr, &split) >= 0) return false;
     SideWgrads sw;
     return plan_side_wgrad(sw, ride, B, T, compute_dtype);
 }

@@ -1,5 +1,5 @@
 // The wide form of the GCN layer backward-data (wide_bwd_kernel below), next to the wide forward of wide_kernels.hip and built from the same
-// phases of the row tile (rowtile_phases.h).
+// phases of the row tile (rowtile_phases.h).  Its k-loop, epilogue, row stores and LDS layout are the forward transform's: wide_common.h.
 #include "wide_common.h"
 
 namespace gcnpt {
@@ -23,19 +23,13 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_bwd_kernel(const RowTilePar
     constexpr bool MASKED = !DZIN;                      // the loader computes dZ = dY * 1[Y>0] * scale / (deg+1) itself
     constexpr bool TWO = MASKED && sizeof(IT) == 4;     // the backward row tile's rounds: two fp32 streams per row, fewer rows in flight
     constexpr int NBU = TWO ? 2 : 4, ITEMS = TWO ? 2 : 3;
-    constexpr int KSTEP = sizeof(CT) == 2 ? 32 : 16;    // K consumed per fragment
-    constexpr int AW = sizeof(CT) == 2 ? 8 : 4;         // CT elements per lane per k-step (16 bytes)
     const int tile_id = (int)blockIdx.x, n_blocks = (int)gridDim.x, r0 = tile_id * ROWS;
-    const int c_lo = (int)blockIdx.y * WIDE_COLS;
-    const int stride = wide_s_stride((int)sizeof(CT));
-    const int ostride = out_stride_dw(WIDE_COLS * (int)sizeof(OT) / 4) * 4 / (int)sizeof(OT);
-    const size_t g_bytes = (size_t)ROWS * stride * sizeof(CT);
-    const size_t s_bytes = std::max(g_bytes, (size_t)ROWS * ostride * sizeof(OT));
+    const WideLds L = wide_lds((int)sizeof(CT), (int)sizeof(OT), p.frag_out != nullptr, false);
+    const int stride = L.stride;
     CT* S = reinterpret_cast<CT*>(smem_raw);            // the chunk of G
     OT* O = reinterpret_cast<OT*>(smem_raw);            // the out tile takes its place after the last k-step
-    CT* Z = reinterpret_cast<CT*>(smem_raw + s_bytes);  // with z_frag: the chunk of the tile's own dZ rows (the image's source)
-    int* meta = reinterpret_cast<int*>(smem_raw + s_bytes + (p.frag_out ? g_bytes : 0));
-    const TileMeta m = tile_meta(meta);
+    CT* Z = reinterpret_cast<CT*>(smem_raw + L.z);      // with z_frag: the chunk of the tile's own dZ rows (the image's source)
+    const TileMeta m = tile_meta(reinterpret_cast<int*>(smem_raw + L.z + L.z_bytes));
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool emit = p.frag_out && blockIdx.y == 0;
 
@@ -83,91 +77,15 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_bwd_kernel(const RowTilePar
         return;
     }
 
-    const int n_tiles = ceil_div(p.NOUT, 16), ksteps = p.Kpad / KSTEP;
-    const uint4* wfrag = static_cast<const uint4*>(p.wfrag);
-    int tl[WIDE_NTW];                                   // this wave's output column tiles (past the last one: duplicates, not stored)
-#pragma unroll
-    for (int j = 0; j < WIDE_NTW; ++j) tl[j] = min((int)blockIdx.y * WIDE_WAVES * WIDE_NTW + j * WIDE_WAVES + wave, n_tiles - 1);
-    f32x4_t acc[2][WIDE_NTW];
-#pragma unroll
-    for (int j = 0; j < WIDE_NTW; ++j) { acc[0][j] = (f32x4_t){0, 0, 0, 0}; acc[1][j] = (f32x4_t){0, 0, 0, 0}; }
-    const int arow = lane & 15, kgrp = lane >> 4;
-
-    // the weight fragments of block b (WIDE_KB k-steps, clamped to the last k-step: always valid memory), and the block's k-steps on the
-    // matrix cores, weights as A (as in the row tile).  Blocks never straddle a chunk; a block that starts a chunk gathers it first
-    constexpr int CKS = WIDE_KCHUNK / KSTEP;            // k-steps per chunk
-    static_assert(CKS % WIDE_KB == 0, "a block of weight fragments never straddles a chunk");
-    typedef uint4 WBlock[WIDE_KB][WIDE_NTW];
-    auto load_block = [&](WBlock& w, int b) {
-#pragma unroll
-        for (int ks = 0; ks < WIDE_KB; ++ks)
-#pragma unroll
-            for (int j = 0; j < WIDE_NTW; ++j) w[ks][j] = wfrag[((size_t)tl[j] * ksteps + min(b * WIDE_KB + ks, ksteps - 1)) * 64 + lane];
-    };
-    const int n_blk = ceil_div(ksteps, WIDE_KB);
-    auto run_block = [&](const WBlock& w, int b) {
-        if (b >= n_blk) return;                         // workgroup-uniform
-        const int kk0 = b * WIDE_KB;
-        if (kk0 % CKS == 0) gather_chunk(kk0 * KSTEP);
-        const int kl0 = (kk0 % CKS) * KSTEP;            // the block's first column inside the chunk
-#pragma unroll
-        for (int ks = 0; ks < WIDE_KB; ++ks) {
-            if (kk0 + ks < ksteps) {                    // wave-uniform
-                const int kl = kl0 + ks * KSTEP + kgrp * AW;
-                const uint4 a0u = *reinterpret_cast<const uint4*>(S + (size_t)arow * stride + kl);
-                const uint4 a1u = *reinterpret_cast<const uint4*>(S + (size_t)(arow + 16) * stride + kl);
-#pragma unroll
-                for (int j = 0; j < WIDE_NTW; ++j) {
-                    if constexpr (sizeof(CT) == 2) {
-                        const bf16x8_t bq = __builtin_bit_cast(bf16x8_t, w[ks][j]);
-                        acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq, __builtin_bit_cast(bf16x8_t, a0u), acc[0][j], 0, 0, 0);
-                        acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq, __builtin_bit_cast(bf16x8_t, a1u), acc[1][j], 0, 0, 0);
-                    } else {
-                        const f32x4_t bq = __builtin_bit_cast(f32x4_t, w[ks][j]);
-                        const f32x4_t a0 = __builtin_bit_cast(f32x4_t, a0u), a1 = __builtin_bit_cast(f32x4_t, a1u);
-#pragma unroll
-                        for (int s = 0; s < 4; ++s) {
-                            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[s], a0[s], acc[0][j], 0, 0, 0);
-                            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(bq[s], a1[s], acc[1][j], 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
-    };
-    WBlock wa, wb;
-    load_block(wa, 0);
-    for (int b = 0; b < n_blk; b += 2) {
-        load_block(wb, b + 1);
-        run_block(wa, b);
-        load_block(wa, b + 2);
-        run_block(wb, b + 1);
-    }
-
-    // the row tile's backward epilogue into the out tile (in S's place), then whole rows leave in 16-byte pieces (with relu_src: as the
-    // layer below's dZ)
-    __syncthreads();
-    float den[2], inv[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) { den[mt] = m.rden[mt * 16 + (lane & 15)]; inv[mt] = m.rinv[mt * 16 + (lane & 15)]; }
-#pragma unroll
-    for (int j = 0; j < WIDE_NTW; ++j) {
-        const int t = (int)blockIdx.y * WIDE_WAVES * WIDE_NTW + j * WIDE_WAVES + wave;
-        if (t >= n_tiles) continue;
-        const int col0 = t * 16 + (lane >> 4) * 4;
-        const f32x4_t aj[2] = {acc[0][j], acc[1][j]};
-        epilogue_tile<OT, true>(p, aj, col0, col0 - c_lo, r0, den, inv, nullptr, O, ostride, 0, lane);
-    }
-    __syncthreads();
-    store_tile_rows<OT, true, WIDE_THREADS>(p, O, ostride, m.rden, r0, c_lo, min(p.NOUT, c_lo + WIDE_COLS) - c_lo, tid);
+    // the weight-block MFMA loop over all k-steps, the chunk of G gathered where a block starts one; then the row tile's backward
+    // epilogue and row stores (with relu_src: as the layer below's dZ)
+    const WideAcc acc = wide_mfma(p, S, stride, wave, lane, gather_chunk);
+    wide_store<OT, true>(p, m, acc, O, L.ostride, nullptr, 0, tid, lane, wave);
 }
 
 template <typename CT, typename IT, typename OT, int VEC, bool DZIN>
 static int wide_bwd_launch_vec(hipStream_t s, const RowTileParams& p) {
-    const int stride = wide_s_stride((int)sizeof(CT));
-    const int ostride = out_stride_dw(WIDE_COLS * (int)sizeof(OT) / 4) * 4 / (int)sizeof(OT);
-    const size_t g_bytes = (size_t)ROWS * stride * sizeof(CT);
-    const size_t lds = std::max(g_bytes, (size_t)ROWS * ostride * sizeof(OT)) + (p.frag_out ? g_bytes : 0) + (size_t)TILE_META_INTS * sizeof(int);
+    const size_t lds = wide_lds((int)sizeof(CT), (int)sizeof(OT), p.frag_out != nullptr, false).bytes;
     const dim3 g(ceil_div(p.N, ROWS), p.out ? ceil_div(ceil_div(p.NOUT, 16), WIDE_WAVES * WIDE_NTW) : 1);
     auto kern = wide_bwd_kernel<CT, IT, OT, VEC, DZIN>;
     GCNPT_LDS_ATTR_ONCE(kern, 160 * 1024);
@@ -190,13 +108,9 @@ static int wide_bwd_launch_t(hipStream_t s, const RowTileParams& p, bool dzin) {
 }
 
 int wide_bwd_launch(hipStream_t s, const RowTileParams& p, int in_dtype, int out_dtype, int compute, bool dzin) {
-    if (compute == GCNPT_F32) {
-        if (in_dtype != GCNPT_F32 || out_dtype != GCNPT_F32) return fail(GCNPT_E_UNSUPPORTED, "compute_dtype f32 needs f32 activations");
-        return wide_bwd_launch_t<float, float, float>(s, p, dzin);
-    }
-    if (in_dtype == GCNPT_F32)
-        return out_dtype == GCNPT_F32 ? wide_bwd_launch_t<bf16_t, float, float>(s, p, dzin) : wide_bwd_launch_t<bf16_t, float, bf16_t>(s, p, dzin);
-    return out_dtype == GCNPT_F32 ? wide_bwd_launch_t<bf16_t, bf16_t, float>(s, p, dzin) : wide_bwd_launch_t<bf16_t, bf16_t, bf16_t>(s, p, dzin);
+    return with_combo(precision_combo(compute, in_dtype, out_dtype), [&](auto ct, auto it, auto ot) {
+        return wide_bwd_launch_t<decltype(ct), decltype(it), decltype(ot)>(s, p, dzin);
+    });
 }
 
 }  // namespace gcnpt

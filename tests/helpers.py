@@ -1,4 +1,6 @@
-"""Shared by the CPU and GPU test modules: rebuild fixture inputs, tolerances."""
+"""Shared by the CPU and GPU test modules: rebuild fixture inputs, tolerances, device helpers, the row tile's LDS count."""
+import contextlib
+
 import numpy as np
 
 from conftest import dense_from_coo, load_golden
@@ -45,3 +47,84 @@ def layer_case(name):
 
 
 LAYER_CASES = ["layers_c1_l1.npz", "layers_c1_l2.npz", "layers_c2s.npz", "layers_c3s.npz", "layers_c5s.npz"]
+
+
+# ---- GPU test modules: the bodies of their `dev` / `api` fixtures, host arrays to the device, pruned trees, scoped options ----
+def cuda_dev():
+    import torch
+    assert torch.cuda.is_available(), "gpu-marked tests need the MI355X"
+    return torch.device("cuda:0")
+
+
+def gcn_api():
+    from gcn_over_pruned_trees_amd import _lib
+    from gcn_over_pruned_trees_amd.model import gcn, tree
+    _lib.lib()
+    return gcn, tree
+
+
+def to_dev(a, dev):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def prune(tree, tb, K, dev):
+    T = tb["head"].shape[1]
+    masks = np.arange(T)[None, :] >= tb["lens"][:, None]
+    return tree.prune_to_csr(to_dev(tb["head"], dev), to_dev(tb["subj_pos"], dev), to_dev(tb["obj_pos"], dev), to_dev(tb["deprel"], dev), K,
+                             masks=to_dev(masks, dev))
+
+
+@contextlib.contextmanager
+def options(**kv):
+    """gcnpt_set_option for the duration of a with-block, keys by name: options(WIDE_BWD=1, DETERMINISTIC=1)."""
+    from gcn_over_pruned_trees_amd import _lib
+    old = []
+    try:
+        for k, v in kv.items():
+            key = getattr(_lib, "OPT_" + k)
+            old.append((key, _lib.set_option(key, v)))
+        yield
+    finally:
+        for key, v in reversed(old):
+            _lib.set_option(key, v)
+
+
+# ---- a restatement of rowtile_shape + rowtile_lds_bytes (csrc/rowtile_body.h), default options ----
+ROWS, WAVE, LDS_MAX = 32, 64, 160 * 1024
+
+
+def _lds_stride_dw(payload):
+    s = -(-payload // 4) * 4
+    while (s & 15) != 8:
+        s += 4
+    return s
+
+
+def _out_stride_dw(payload):
+    s = -(-payload // 4) * 4
+    while (s & 7) != 4:
+        s += 4
+    return s
+
+
+def rowtile_lds(N, K, NOUT, ct, ot, vec, bwd):
+    """LDS bytes the one-shot row tile asks for over N rows: the contraction runs over K (forward: Din; backward-data: H), the output
+    is NOUT wide (forward: H; backward-data: Din); ct / ot bytes of the MFMA operand / output; rows read by vectors (vec) or element
+    by element.  The S tile, the out tile (bwd: the larger of it and the Z tile, two tiles of width K), the adjacency tables, the bias
+    of a column pass."""
+    kstep = 32 if ct == 2 else 16
+    kpad = -(-K // kstep) * kstep
+    n_tiles = -(-NOUT // 16)
+    four = vec and -(-N // ROWS) > 256 and (n_tiles <= 24 or -(-n_tiles // 20) <= -(-n_tiles // 32))
+    if not vec:
+        nwv, ntw = 8, 4
+    elif four:
+        nwv, ntw = 4, (2 if n_tiles <= 8 else 3 if n_tiles <= 12 else 4 if n_tiles <= 16 else 6 if 20 < n_tiles <= 24 else 5)
+    else:
+        nwv, ntw = 8, (2 if n_tiles <= 16 else 3 if n_tiles <= 24 else 4)
+    stride = _lds_stride_dw(kpad * ct // 4) * 4 // ct
+    ncols = nwv * ntw * 16
+    ostride = _out_stride_dw(min(-(-NOUT // 16) * 16, ncols) * ot // 4) * 4 // ot
+    s_bytes, o_bytes = ROWS * stride * ct, ROWS * ostride * ot
+    return s_bytes + (max(s_bytes, o_bytes) if bwd else o_bytes) + ROWS * 13 * 4 + max(nwv * WAVE, ncols) * 4

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import FWD_RTOL, GRAD_RTOL, max_rel
+from helpers import FWD_RTOL, GRAD_RTOL, cuda_dev, gcn_api, max_rel, options, prune, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -18,44 +18,12 @@ BF16_GRAD = 2e-2
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "gpu-marked tests need the MI355X"
-    return torch.device("cuda:0")
+    return cuda_dev()
 
 
 @pytest.fixture(scope="module")
 def api():
-    from gcn_over_pruned_trees_amd import _lib
-    from gcn_over_pruned_trees_amd.model import gcn, tree
-    _lib.lib()
-    return gcn, tree
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _prune(tree, tb, K, dev):
-    T = tb["head"].shape[1]
-    masks = np.arange(T)[None, :] >= tb["lens"][:, None]
-    return tree.prune_to_csr(_t(tb["head"], dev), _t(tb["subj_pos"], dev), _t(tb["obj_pos"], dev), _t(tb["deprel"], dev), K,
-                             masks=_t(masks, dev))
-
-
-class _Options:
-    """gcnpt_set_option for the duration of a with-block (several keys)."""
-
-    def __init__(self, **kv):
-        from gcn_over_pruned_trees_amd import _lib
-        self.kv = [(getattr(_lib, "OPT_" + k), v) for k, v in kv.items()]
-
-    def __enter__(self):
-        from gcn_over_pruned_trees_amd import _lib
-        self.old = [(k, _lib.set_option(k, v)) for k, v in self.kv]
-
-    def __exit__(self, *exc):
-        from gcn_over_pruned_trees_amd import _lib
-        for k, v in reversed(self.old):
-            _lib.set_option(k, v)
+    return gcn_api()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -74,8 +42,8 @@ def _oracle_case(api, dev, shape, layout, compute, drop=0.0, no_adj=False):
     tb = synthetic.random_tree_batch(500 + B + T + hid, B, T, "tacred")
     Wn, bn = synthetic.layer_params(21 + hid, [din, hid, hid])
     xn, gyn = synthetic.normal(22, (B, T, din)), synthetic.normal(23, (B, T, hid))
-    trees = _prune(tree, tb, K, dev)
-    x0, g0 = _t(xn, dev), _t(gyn, dev)
+    trees = prune(tree, tb, K, dev)
+    x0, g0 = to_dev(xn, dev), to_dev(gyn, dev)
     real = np.arange(T)[None, :] < tb["lens"][:, None]
     if layout == "compact":             # the kept tokens only: a [B, Tc] batch of its own, checked against the oracle on that batch
         ct = trees.compact()
@@ -84,13 +52,13 @@ def _oracle_case(api, dev, shape, layout, compute, drop=0.0, no_adj=False):
         xn, gyn = x0.cpu().numpy(), g0.cpu().numpy()
         real = ct.valid.cpu().numpy()
     adj = trees.to_dense().cpu().numpy().astype(np.float32)
-    keep = _t(real, dev)
+    keep = to_dev(real, dev)
     if layout == "packed":
         trees = trees.pack(tb["lens"].tolist())
         x0, g0 = x0[keep].contiguous(), g0[keep].contiguous()
     x = x0.clone().requires_grad_()
-    Ws = [_t(w, dev).requires_grad_() for w in Wn]
-    bs = [_t(b, dev).requires_grad_() for b in bn]
+    Ws = [to_dev(w, dev).requires_grad_() for w in Wn]
+    bs = [to_dev(b, dev).requires_grad_() for b in bn]
     h, acts = gcn.gcn_layers_with_acts(x, Ws, bs, trees, drop_p=[drop, 0.0], seeds=[9, 0], compute_dtype=compute, no_adj=no_adj)
     h.backward(g0)
     torch.cuda.synchronize()
@@ -212,11 +180,11 @@ def _stack_case(api, dev, B, T, din, hid, compute, x_dtype, mid, out_dtype, seed
     from gcn_over_pruned_trees_amd.utils import synthetic
     _, tree = api
     tb = synthetic.random_tree_batch(seed, B, T, "tacred")
-    trees = _prune(tree, tb, 1, dev)
+    trees = prune(tree, tb, 1, dev)
     Wn, bn = synthetic.layer_params(seed + 1, [din, hid, hid])
-    x = _t(synthetic.normal(seed + 2, (B, T, din)), dev).to(x_dtype)
-    st = _Stack(dev, trees, B, T, x, [_t(w, dev) for w in Wn], [_t(b, dev) for b in bn], compute, mid, out_dtype, 0.3)
-    gy = _t(synthetic.normal(seed + 3, (B, T, hid)), dev).to(out_dtype)
+    x = to_dev(synthetic.normal(seed + 2, (B, T, din)), dev).to(x_dtype)
+    st = _Stack(dev, trees, B, T, x, [to_dev(w, dev) for w in Wn], [to_dev(b, dev) for b in bn], compute, mid, out_dtype, 0.3)
+    gy = to_dev(synthetic.normal(seed + 3, (B, T, hid)), dev).to(out_dtype)
     # a ready-made top dZ (what gcnpt_pool3_bwd_dz leaves): zero where the top layer's output is, like the real one
     dz = torch.where(st.outs[1] > 0, gy.float() * 0.25, torch.zeros_like(gy.float())).to(out_dtype)
     return st, gy, dz
@@ -256,7 +224,7 @@ def test_forced_wide_bwd_matches_row_tile(api, dev, case, entry):
     g = dz if entry == "dz" else gy
     res = []
     for form in (0, 1):
-        with _Options(WIDE_BWD=form, DETERMINISTIC=1):
+        with options(WIDE_BWD=form, DETERMINISTIC=1):
             res.append(st.bwd(g, entry == "dz"))
     (dha, zfa, dWa, dba), (dhb, zfb, dWb, dbb) = res
     cd = st.cd
@@ -283,7 +251,7 @@ def test_sweep_in_pieces(api, dev, wide, entry):
     hid = 200 if wide == 1 else 768
     st, gy, dz = _stack_case(api, dev, 12, 40, 360, hid, *(torch.float32,) * 4, 700 + hid)
     g = dz if entry == "dz" else gy
-    with _Options(WIDE_BWD=wide, DETERMINISTIC=1):
+    with options(WIDE_BWD=wide, DETERMINISTIC=1):
         whole = st.bwd(g, entry == "dz")
         parts = st.bwd(g, entry == "dz", pieces=4)
     for l in range(2):
@@ -301,17 +269,17 @@ def test_option_zero_brings_the_refusal_back(api, dev):
     gcn, tree = api
     B, T = 2, 30
     tb = synthetic.random_tree_batch(5, B, T, "tacred")
-    trees = _prune(tree, tb, 1, dev)
+    trees = prune(tree, tb, 1, dev)
     Wn, bn = synthetic.layer_params(6, [360, 768, 768])
-    x = _t(synthetic.normal(7, (B, T, 360)), dev)
+    x = to_dev(synthetic.normal(7, (B, T, 360)), dev)
 
     def run():
-        Ws = [_t(w, dev).requires_grad_() for w in Wn]
-        bs = [_t(b, dev).requires_grad_() for b in bn]
+        Ws = [to_dev(w, dev).requires_grad_() for w in Wn]
+        bs = [to_dev(b, dev).requires_grad_() for b in bn]
         gcn.gcn_layers(x, Ws, bs, trees).sum().backward()
         return Ws
 
-    with _Options(WIDE_BWD=0):
+    with options(WIDE_BWD=0):
         with pytest.raises(_lib.GcnptError) as e:
             run()
         assert e.value.code == _lib.E_UNSUPPORTED and b"LDS" in str(e.value).encode()
@@ -366,10 +334,10 @@ def test_wide_hidden_classifier_golden(api, dev, packed):
     model = gcn.GCNClassifier(opt)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
     model = model.to(dev).train()
-    logits, pooled = model(tuple(_t(a, dev) for a in batch))
+    logits, pooled = model(tuple(to_dev(a, dev) for a in batch))
     seed = int(g["seed"])
-    g_logits = _t(synthetic.normal(seed + 3, tuple(logits.shape)), dev)
-    g_pooled = _t(synthetic.normal(seed + 4, tuple(pooled.shape)), dev)
+    g_logits = to_dev(synthetic.normal(seed + 3, tuple(logits.shape)), dev)
+    g_pooled = to_dev(synthetic.normal(seed + 4, tuple(pooled.shape)), dev)
     ((logits * g_logits).sum() + (pooled * g_pooled).sum()).backward()
     torch.cuda.synchronize()
     assert max_rel(logits.detach().cpu().numpy(), g["logits"]) <= 1e-4
@@ -403,8 +371,8 @@ def test_wide_hidden_training_step_capture(api, dev):
     ner = rng.randint(2, 15, size=(B, T)).astype(np.int64)
     for a in (words, pos, ner):
         a[tb["masks"]] = 0
-    inputs = tuple(_t(a, dev) for a in (words, tb["masks"], pos, ner, tb["deprel"], tb["head"], tb["subj_pos"], tb["obj_pos"]))
-    labels = _t(rng.randint(0, 42, size=(B,)).astype(np.int64), dev)
+    inputs = tuple(to_dev(a, dev) for a in (words, tb["masks"], pos, ner, tb["deprel"], tb["head"], tb["subj_pos"], tb["obj_pos"]))
+    labels = to_dev(rng.randint(0, 42, size=(B,)).astype(np.int64), dev)
     opt = dict(vocab_size=40, emb_dim=300, pos_dim=30, ner_dim=30, hidden_dim=768, num_layers=2, input_dropout=0.0, gcn_dropout=0.0,
                word_dropout=0.0, emb_dropout=0.0, topn=1e10, prune_k=1, pooling="max", pooling_l2=0.003, mlp_layers=2, no_adj=False,
                rnn=False, cuda=True, dataset="tacred", num_class=42, adj_type="regular", gcn_dtype="fp32", gcn_check_trees=False)
@@ -420,7 +388,7 @@ def test_wide_hidden_training_step_capture(api, dev):
         loss.backward()
         return loss.detach()
 
-    with _Options(DETERMINISTIC=1):
+    with options(DETERMINISTIC=1):
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):

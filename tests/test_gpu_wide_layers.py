@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import FWD_RTOL, GRAD_RTOL, max_rel
+from helpers import FWD_RTOL, GRAD_RTOL, cuda_dev, gcn_api, max_rel, options, prune, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -18,42 +18,12 @@ BF16_GRAD = 2e-2
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "gpu-marked tests need the MI355X"
-    return torch.device("cuda:0")
+    return cuda_dev()
 
 
 @pytest.fixture(scope="module")
 def api():
-    from gcn_over_pruned_trees_amd import _lib
-    from gcn_over_pruned_trees_amd.model import gcn, tree
-    _lib.lib()
-    return gcn, tree
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _prune(tree, tb, K, dev):
-    T = tb["head"].shape[1]
-    masks = np.arange(T)[None, :] >= tb["lens"][:, None]
-    return tree.prune_to_csr(_t(tb["head"], dev), _t(tb["subj_pos"], dev), _t(tb["obj_pos"], dev), _t(tb["deprel"], dev), K,
-                             masks=_t(masks, dev))
-
-
-class _Option:
-    """gcnpt_set_option for the duration of a with-block."""
-
-    def __init__(self, key, value):
-        self.key, self.value = key, value
-
-    def __enter__(self):
-        from gcn_over_pruned_trees_amd import _lib
-        self.old = _lib.set_option(self.key, self.value)
-
-    def __exit__(self, *exc):
-        from gcn_over_pruned_trees_amd import _lib
-        _lib.set_option(self.key, self.old)
+    return gcn_api()
 
 
 # (B, T, Din, H, K): BERT-large + POS + NER; a 300-wide hidden layer; K = 0 trees; 4096 columns; a second output-column slice
@@ -77,15 +47,15 @@ def test_wide_layers_vs_oracle(api, dev, shape, layout, compute):
     adj = prune_ref.batch_adj(tb["head"], tb["subj_pos"], tb["obj_pos"], tb["deprel"], tb["lens"], K)["adj"]
     Wn, bn = synthetic.layer_params(11, [din, hid, hid])
     xn, gyn = synthetic.normal(12, (B, T, din)), synthetic.normal(13, (B, T, hid))
-    trees = _prune(tree, tb, K, dev)
-    x0, g0 = _t(xn, dev), _t(gyn, dev)
-    keep = ~_t(np.arange(T)[None, :] >= tb["lens"][:, None], dev)
+    trees = prune(tree, tb, K, dev)
+    x0, g0 = to_dev(xn, dev), to_dev(gyn, dev)
+    keep = ~to_dev(np.arange(T)[None, :] >= tb["lens"][:, None], dev)
     if layout == "packed":
         trees = trees.pack(tb["lens"].tolist())
         x0, g0 = x0[keep].contiguous(), g0[keep].contiguous()
     x = x0.clone().requires_grad_()
-    Ws = [_t(w, dev).requires_grad_() for w in Wn]
-    bs = [_t(b, dev).requires_grad_() for b in bn]
+    Ws = [to_dev(w, dev).requires_grad_() for w in Wn]
+    bs = [to_dev(b, dev).requires_grad_() for b in bn]
     h, acts = gcn.gcn_layers_with_acts(x, Ws, bs, trees, compute_dtype=compute)
     h.backward(g0)
     torch.cuda.synchronize()
@@ -149,26 +119,26 @@ def test_forced_wide_form_matches_row_tile(api, dev, case, layout, compute):
     B, T, din, lengths = case
     hid, K = 200, 1
     tb = synthetic.random_tree_batch(77 + B, B, T, lengths)
-    trees = _prune(tree, tb, K, dev)
+    trees = prune(tree, tb, K, dev)
     Wn, bn = synthetic.layer_params(78, [din, hid, hid])
     xn, gyn = synthetic.normal(79, (B, T, din)), synthetic.normal(80, (B, T, hid))
-    x0, g0 = _t(xn, dev), _t(gyn, dev)
+    x0, g0 = to_dev(xn, dev), to_dev(gyn, dev)
     if layout == "packed":
-        keep = ~_t(tb["masks"], dev)
+        keep = ~to_dev(tb["masks"], dev)
         trees = trees.pack(tb["lens"].tolist())
         x0, g0 = x0[keep].contiguous(), g0[keep].contiguous()
     if compute == torch.bfloat16:
         x0 = x0.to(torch.bfloat16)
     cd = _lib.dtype_code(compute)
-    Wt = [_t(w, dev) for w in Wn]
-    bt = [_t(b, dev) for b in bn]
+    Wt = [to_dev(w, dev) for w in Wn]
+    bt = [to_dev(b, dev) for b in bn]
     pk = WeightPack(Wt, cd, dev)
     _lib.check(_lib.lib().gcnpt_pack_weights_multi(_lib.stream(), *pk.c_args()))
     seed_dev = torch.tensor([12345], dtype=torch.int64, device=dev)
     dims = [(hid, din), (hid, hid)]
     res, grads = [], []
     for form in (0, 1):
-        with _Option(_lib.OPT_WIDE_FORM, form):
+        with options(WIDE_FORM=form):
             res.append(_stack_fwd(_lib, 2, x0, pk.wf, bt, trees, dims, cd, [0.3, 0.0], [5, 0], seed_dev, torch.float32))
             x = x0.clone().float().requires_grad_() if compute == torch.float32 else x0.clone().requires_grad_()
             Ws = [w.clone().requires_grad_() for w in Wt]
@@ -196,11 +166,11 @@ def test_option_zero_brings_the_refusal_back(api, dev):
     gcn, tree = api
     B, T = 2, 30
     tb = synthetic.random_tree_batch(5, B, T, "tacred")
-    trees = _prune(tree, tb, 1, dev)
+    trees = prune(tree, tb, 1, dev)
     Wn, bn = synthetic.layer_params(6, [1084, 200])
-    x = _t(synthetic.normal(7, (B, T, 1084)), dev)
-    Ws, bs = [_t(w, dev) for w in Wn], [_t(b, dev) for b in bn]
-    with _Option(_lib.OPT_WIDE_FORM, 0):
+    x = to_dev(synthetic.normal(7, (B, T, 1084)), dev)
+    Ws, bs = [to_dev(w, dev) for w in Wn], [to_dev(b, dev) for b in bn]
+    with options(WIDE_FORM=0):
         with pytest.raises(_lib.GcnptError) as e:
             gcn.gcn_layers(x, Ws, bs, trees)
         assert e.value.code == _lib.E_UNSUPPORTED and b"LDS" in str(e.value).encode()
@@ -224,9 +194,9 @@ def _bert_inputs(dev, B, T, seed):
     rng = np.random.RandomState(seed)
     words = rng.standard_normal((B, T, 1024)).astype(np.float32)          # BERT-large vectors (data/bert_embeddings.py's output)
     words[tb["masks"]] = 0.0
-    return (_t(words, dev), _t(tb["masks"], dev), _t(rng.randint(0, 47, size=(B, T)).astype(np.int64), dev),
-            _t(rng.randint(0, 15, size=(B, T)).astype(np.int64), dev), _t(tb["deprel"], dev), _t(tb["head"], dev),
-            _t(tb["subj_pos"], dev), _t(tb["obj_pos"], dev)), tb
+    return (to_dev(words, dev), to_dev(tb["masks"], dev), to_dev(rng.randint(0, 47, size=(B, T)).astype(np.int64), dev),
+            to_dev(rng.randint(0, 15, size=(B, T)).astype(np.int64), dev), to_dev(tb["deprel"], dev), to_dev(tb["head"], dev),
+            to_dev(tb["subj_pos"], dev), to_dev(tb["obj_pos"], dev)), tb
 
 
 def _golden_batch(g):
@@ -271,7 +241,7 @@ def test_bert_no_rnn_classifier_golden(api, dev, dtype):
     g = load_golden("e2e_bert_norrn.npz")
     _, batch, sd = _golden_batch(g)
     opt = dict(json.loads(str(g["opt"])), cuda=True, gcn_dtype=dtype)
-    inputs = tuple(_t(a, dev) for a in batch)
+    inputs = tuple(to_dev(a, dev) for a in batch)
 
     def build(**kw):
         m = gcn.GCNClassifier(dict(opt, **kw))
@@ -280,8 +250,8 @@ def test_bert_no_rnn_classifier_golden(api, dev, dtype):
 
     model = build()
     logits, pooled = model(inputs)
-    g_logits = _t(synthetic_normal(int(g["seed"]) + 3, tuple(logits.shape)), dev)
-    g_pooled = _t(synthetic_normal(int(g["seed"]) + 4, tuple(pooled.shape)), dev)
+    g_logits = to_dev(synthetic_normal(int(g["seed"]) + 3, tuple(logits.shape)), dev)
+    g_pooled = to_dev(synthetic_normal(int(g["seed"]) + 4, tuple(pooled.shape)), dev)
     ((logits * g_logits).sum() + (pooled * g_pooled).sum()).backward()
     torch.cuda.synchronize()
     lg = logits.detach().cpu().numpy()
@@ -319,7 +289,7 @@ def test_bert_no_rnn_training_step_capture(api, dev):
     gcn, tree = api
     B, T = 20, 60
     inputs, _ = _bert_inputs(dev, B, T, 123)
-    labels = _t(np.random.RandomState(4).randint(0, 42, size=(B,)).astype(np.int64), dev)
+    labels = to_dev(np.random.RandomState(4).randint(0, 42, size=(B,)).astype(np.int64), dev)
     torch.manual_seed(1234)
     model = gcn.GCNClassifier(_bert_opt(gcn_dropout=0.5, gcn_check_trees=False, gcn_graph_rng=True)).to(dev).train()
     cache = tree.TreeCache.build(inputs[5], inputs[6], inputs[7], inputs[4], 1, masks=inputs[1], want_label=False, compact=True)

@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-ROWS, WAVE, LDS_MAX = 32, 64, 160 * 1024
+from helpers import LDS_MAX, rowtile_lds
 
 
 def _lib():
@@ -14,39 +14,10 @@ def _lib():
     return lib
 
 
-def _lds_stride_dw(payload):
-    s = -(-payload // 4) * 4
-    while (s & 15) != 8:
-        s += 4
-    return s
-
-
-def _out_stride_dw(payload):
-    s = -(-payload // 4) * 4
-    while (s & 7) != 4:
-        s += 4
-    return s
-
-
 def _bwd_lds(N, din, H, ct, ot, vec):
-    """A restatement of rowtile_bwd_too_wide's byte count (rowtile_shape + rowtile_lds_bytes, csrc/rowtile_body.h) for a backward-data
-    launch, default options: the contraction runs over H (Kpad), the output is Din wide; rows read by vectors (vec) or element by
-    element.  Two tiles of width H (the gathered one and the Z / out tile), the adjacency tables, the bias of a column pass."""
-    kstep = 32 if ct == 2 else 16
-    kpad = -(-H // kstep) * kstep
-    n_tiles = -(-din // 16)
-    four = vec and -(-N // ROWS) > 256 and (n_tiles <= 24 or -(-n_tiles // 20) <= -(-n_tiles // 32))
-    if not vec:
-        nwv, ntw = 8, 4
-    elif four:
-        nwv, ntw = 4, (2 if n_tiles <= 8 else 3 if n_tiles <= 12 else 4 if n_tiles <= 16 else 6 if 20 < n_tiles <= 24 else 5)
-    else:
-        nwv, ntw = 8, (2 if n_tiles <= 16 else 3 if n_tiles <= 24 else 4)
-    stride = _lds_stride_dw(kpad * ct // 4) * 4 // ct
-    ncols = nwv * ntw * 16
-    ostride = _out_stride_dw(min(-(-din // 16) * 16, ncols) * ot // 4) * 4 // ot
-    s_bytes, o_bytes = ROWS * stride * ct, ROWS * ostride * ot
-    return s_bytes + max(s_bytes, o_bytes) + ROWS * 13 * 4 + max(nwv * WAVE, ncols) * 4
+    """rowtile_bwd_too_wide's byte count (rowtile_shape + rowtile_lds_bytes, csrc/rowtile_body.h) for a backward-data launch: the
+    contraction runs over H (Kpad), the output is Din wide."""
+    return rowtile_lds(N, H, din, ct, ot, vec, True)
 
 
 def _refused_vec(N, din, H, ct, ot, vec):

@@ -4,26 +4,12 @@ import ctypes
 
 import pytest
 
-ROWS, WAVE, LDS_MAX = 32, 64, 160 * 1024
+from helpers import LDS_MAX, rowtile_lds
 
 
 def _lib():
     from gcn_over_pruned_trees_amd import _lib as lib
     return lib
-
-
-def _lds_stride_dw(payload):
-    s = -(-payload // 4) * 4
-    while (s & 15) != 8:
-        s += 4
-    return s
-
-
-def _out_stride_dw(payload):
-    s = -(-payload // 4) * 4
-    while (s & 7) != 4:
-        s += 4
-    return s
 
 
 def _refused(N, din, H, ct, ot=4):
@@ -32,23 +18,9 @@ def _refused(N, din, H, ct, ot=4):
 
 
 def _refused_vec(N, din, H, ct, ot, vec):
-    """A restatement of rowtile_shape + rowtile_lds_bytes (csrc/rowtile_body.h) for a forward layer, default options, rows read by
-    vectors (vec) or element by element: does the one-shot row tile ask for more than 160 KiB of LDS?"""
-    kstep = 32 if ct == 2 else 16
-    kpad = -(-din // kstep) * kstep
-    n_tiles = -(-H // 16)
-    four = vec and -(-N // ROWS) > 256 and (n_tiles <= 24 or -(-n_tiles // 20) <= -(-n_tiles // 32))
-    if not vec:
-        nwv, ntw = 8, 4
-    elif four:
-        nwv, ntw = 4, (2 if n_tiles <= 8 else 3 if n_tiles <= 12 else 4 if n_tiles <= 16 else 6 if 20 < n_tiles <= 24 else 5)
-    else:
-        nwv, ntw = 8, (2 if n_tiles <= 16 else 3 if n_tiles <= 24 else 4)
-    stride = _lds_stride_dw(kpad * ct // 4) * 4 // ct
-    ncols = nwv * ntw * 16
-    ostride = _out_stride_dw(min(-(-H // 16) * 16, ncols) * ot // 4) * 4 // ot
-    lds = ROWS * stride * ct + ROWS * ostride * ot + ROWS * 13 * 4 + max(nwv * WAVE, ncols) * 4
-    return lds > LDS_MAX
+    """rowtile_shape + rowtile_lds_bytes (csrc/rowtile_body.h) for a forward layer: does the one-shot row tile ask for more than
+    160 KiB of LDS?"""
+    return rowtile_lds(N, din, H, ct, ot, vec, False) > LDS_MAX
 
 
 def test_wide_form_option():
