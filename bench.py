@@ -2,7 +2,7 @@
 """
 bench.py -- BASELINE.json metric: GCN-layer fwd+bwd sentences/sec at batch=50 seq=100 h=200 on N MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run, or self-launched)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run, or self-launched)
 
 One "step" = the hot path over one synthetic TACRED-shaped batch of 50 sentences x 100 tokens
 (BASELINE.json configs[1]: 2-layer GCN, no LSTM, Din 360 -> 200 -> 200, prune_k 1, bf16 storage,
@@ -10,17 +10,20 @@ fp32 accumulation, dropout 0.5 between the layers), entirely through the C-ABI o
     pack W0+W1 -> layer0 fwd -> layer1 fwd -> layer1 bwd-data -> layer0 bwd-data with layer1's weight gradient riding -> layer0 bwd-weight
 (six launches from ONE native call, gcnpt_layers_step, whose argument struct is marshalled once).
 Inputs (x, gy, weights, the loader's integer tensors) are resident in HBM before the timed region.
-`value` is the layer stack alone, as the metric says; `with_prune` / `with_cached_trees` repeat the measurement with the
-pruned-tree adjacency build / its assembly from a pre-pruned dataset inside every step.
+`value` is the layer stack alone, as the metric says; with --full, `with_prune` / `with_cached_trees` repeat the measurement with
+the pruned-tree adjacency build / its assembly from a pre-pruned dataset inside every step.
 
 For N > 1 every rank runs its own 50-sentence shard (weak scaling, no data-path collective) as SYNCHRONOUS data-parallel SGD
 (BASELINE.json configs[3]; the reference updates every step at batch 50, train.py:209,224-227): the flat gradient bucket
 [dW0,db0,dW1,db1] is all-reduced over RCCL, W -= lr * g runs on the device, and the next step's weight pack reads the updated
 weights -- step i+1 depends on all-reduce i.  (`async_upper_bound` in the line is the free-running ring of round 2, where nothing
-consumes the reduced gradient: NOT synchronous SGD, reported as a labelled secondary only.)
+consumes the reduced gradient: NOT synchronous SGD, reported as a labelled secondary only, with --full.)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant kernel, `launch_floor_us` (the
-same launches with empty bodies) and `cpu_baseline` (the CPU oracle on this box's cores).
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set-up, the launch-mode trial of the
+warm-up, the W + K steps, --dump-outputs, the line.  --full adds every other measurement to it: the repeats of the timed region
+(`ms_per_step_median`), the secondary steps (`with_prune`, `with_cached_trees`, `fp32`, `with_pooling`, `packed_rows`,
+`pooled_only_rows`), `roofline` for the dominant kernel with the per-kernel breakdown, `launch_floor_us` (the same launches with
+empty bodies), `secondary_shapes`, `cpu_baseline` (the CPU oracle on the host's cores) and, for N > 1, `async_upper_bound`.
 """
 import argparse
 import copy
@@ -78,7 +81,7 @@ def parse():
     ap.add_argument("--exchange", choices=["sync", "async"], default="sync",
                     help="N > 1.  sync (the headline): all-reduce, device-side SGD update, and the next step's pack waits for both. "
                          "async: the round-2 ring of buckets whose all-reduce nobody consumes -- an upper bound, not data-parallel SGD")
-    ap.add_argument("--repeats", type=int, default=20, help="N = 1: repeats of the timed K-step region behind the contract's one, for ms_per_step_median")
+    ap.add_argument("--repeats", type=int, default=20, help="N = 1, --full: repeats of the timed K-step region behind the contract's one, for ms_per_step_median")
     ap.add_argument("--no-clip", action="store_true", help="N > 1, A/B: plain W -= lr*g instead of the reference's clip_grad_norm_ + SGD update")
     ap.add_argument("--torch-update", action="store_true", help="N > 1, A/B: clip + SGD update through torch's element-wise kernels instead of gcnpt_sgd_clip_update")
     ap.add_argument("--two-step-pack", action="store_true", help="A/B, packed layout with the tree build: gcnpt_prune_to_csr + gcnpt_pack_trees "
@@ -93,6 +96,9 @@ def parse():
                     "with_cached_trees steps instead of a side job of the tree launch")
     ap.add_argument("--no-pooled-only", action="store_true", help="skip the secondary pooled-only-rows measurement (profiling runs: its launches "
                                                                   "would mix into the per-kernel statistics of the headline step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (repeats, secondary steps and shapes, per-kernel breakdown and "
+                         "roofline, launch floor, CPU baseline, the async ring for N > 1); --repeats and the options that skip one of these only act then")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0: layer outputs, input gradients, the gradient bucket "
                          "and, for N > 1, the updated weights) as DIR/<name>.npy in float32, at most 64 MB in all; the inputs are seeded, so "
@@ -718,6 +724,11 @@ def self_launch(args):
 
 def main():
     args = parse()
+    if not args.full:
+        # a plain run is the headline alone: every leg beside it is off (N > 1: the async ring too, below)
+        args.repeats = 0
+        args.no_secondary = args.no_secondary_shapes = args.no_pooled_only = True
+        args.no_kernel_breakdown = args.no_floor = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -859,7 +870,7 @@ def main():
     weight_drift = float((stack.wflat - w0).double().abs().sum().item())      # > 0 iff the SGD updates were applied (N > 1, sync)
 
     async_bound = None
-    if multi and exchange == "sync":
+    if multi and exchange == "sync" and args.full:
         # labelled secondary: the free-running ring (not synchronous SGD)
         stack.wflat.copy_(w0)
         ring = OverlappedAllReduce(stack.buckets, dist, average=False)

@@ -2,7 +2,7 @@
 bench.py as the driver invokes it: `python bench.py --gpus N` must start N ranks itself (the reference has no
 distributed entry point at all, train_cgcn.sh:5 picks one GPU).  CPU tests cover the refusals that need no GPU; the `gpu` test
 runs the real self-launch with two ranks sharing the one GPU of the box over gloo (GCNPT_BENCH_ONE_DEVICE=1).  --dump-outputs: its size
-cap and row sample on the CPU, its arrays against the CPU oracle on the GPU.
+cap and row sample on the CPU, its arrays against the CPU oracle on the GPU.  A plain run against --full: which fields each prints.
 """
 import json
 import os
@@ -49,7 +49,7 @@ def test_self_launch_two_ranks_one_device():
     assert len(l1) == 1
     d1 = json.loads(l1[0])
     assert d1["n_gpus"] == 1
-    two = _run(["--gpus", "2", "--dist-backend", "gloo"] + common,
+    two = _run(["--gpus", "2", "--dist-backend", "gloo", "--full"] + common,                # --full: async_upper_bound beside the headline
                env={"GCNPT_BENCH_ONE_DEVICE": "1", "GCNPT_BENCH_SAME_SHARD": "1"})
     assert two.returncode == 0, two.stderr[-3000:]
     l2 = [ln for ln in two.stdout.decode().splitlines() if ln.startswith("{")]
@@ -65,6 +65,28 @@ def test_self_launch_two_ranks_one_device():
     assert d2["config"]["dp_mode"].startswith("synchronous SGD") and d2["config"]["weight_abs_drift_after_timed_steps"] > 0
     assert "async_upper_bound" in d2 and "NOT synchronous" in d2["async_upper_bound"]["note"]
     assert d1["config"]["dp_mode"] == "none (1 GPU)"
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone_and_full_adds_the_rest():
+    """A plain run prints the headline and nothing that needs runs of its own; --full adds the repeats, the secondary steps and
+    shapes, the per-kernel breakdown with its roofline and launch floor, and the CPU baseline (kept short here)."""
+    extra = ("ms_per_step_repeats", "with_prune", "with_cached_trees", "fp32", "with_pooling", "pooled_only_rows", "roofline", "kernels",
+             "step_roofline", "launch_floor_us", "secondary_shapes", "cpu_baseline")
+    lines = {}
+    for name, flags in (("plain", []), ("full", ["--full", "--repeats", "2", "--cpu-seconds", "0.2"])):
+        r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"] + flags)
+        assert r.returncode == 0, (name, r.stderr[-2000:])
+        ln = [x for x in r.stdout.decode().splitlines() if x.startswith("{")]
+        assert len(ln) == 1, (name, r.stdout[-2000:])
+        lines[name] = json.loads(ln[0])
+    for d in lines.values():
+        assert d["metric"] == "GCN-layer fwd+bwd sentences/sec at batch=50 seq=100 h=200" and d["unit"] == "sentences/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 20 and d["warmup"] == 5
+        assert d["value"] > 0 and abs(d["value"] - 50 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    plain, full = lines["plain"], lines["full"]
+    assert [k for k in extra if plain.get(k) is not None] == [] and plain["ms_per_step_median"] is None, sorted(plain)
+    assert [k for k in extra if full.get(k) is None] == [] and full["ms_per_step_repeats"]["n"] == 2, sorted(full)
 
 
 def test_dump_outputs_stays_under_cap_with_a_fixed_sample(tmp_path):

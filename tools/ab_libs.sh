@@ -7,10 +7,11 @@
 # committed (*.so is ignored).
 set -o pipefail
 LIBS="${LIBS:-libgcnpt.so}"
+TMP=$(mktemp -d)
 for rep in 1 2; do
 for lib in $LIBS; do
-  GCNPT_LIB=$PWD/gcn-over-pruned-trees_amd/csrc/$lib timeout -k 10 200 python bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-pooled-only --no-secondary --no-secondary-shapes --no-floor $BARGS > gpurun_out/b.json 2>gpurun_out/b.err || { tail -3 gpurun_out/b.err; exit 1; }
+  GCNPT_LIB=$PWD/gcn-over-pruned-trees_amd/csrc/$lib timeout -k 10 200 python bench.py --steps 2000 --warmup 200 --full --no-cpu-baseline --no-pooled-only --no-secondary --no-secondary-shapes --no-floor $BARGS > $TMP/b.json 2>$TMP/b.err || { tail -3 $TMP/b.err; exit 1; }
   python -c "
-import json;d=json.loads(open('gpurun_out/b.json').read().strip().split('\n')[-1]);print('$lib', round(d['ms_per_step']*1e3,2), {k:round(v['avg_us'],2) for k,v in d['kernels'].items()})"
+import json;d=json.loads(open('$TMP/b.json').read().strip().split('\n')[-1]);print('$lib', round(d['ms_per_step']*1e3,2), {k:round(v['avg_us'],2) for k,v in d['kernels'].items()})"
 done
 done

@@ -1,7 +1,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/env20
 mkdir -p $OUT
-A="--steps 20 --warmup 5 --repeats 40 --no-cpu-baseline --no-pooled-only --no-secondary --no-secondary-shapes --no-kernel-breakdown --no-floor"
+A="--steps 20 --warmup 5 --full --repeats 40 --no-cpu-baseline --no-pooled-only --no-secondary --no-secondary-shapes --no-kernel-breakdown --no-floor"
 run() {
     name=$1; shift
     ( export "$@"; timeout -k 10 120 python3 $R/bench.py $A > $OUT/$name.json 2> $OUT/$name.err ) || echo "$name failed"
