@@ -159,10 +159,16 @@ class _GCNLayersFn(torch.autograd.Function):
         sp, op, kind = pool
         H = dims[-1][0]
         pm = trees.pool_mask.contiguous()
-        pooled = torch.empty((B, 3 * H), dtype=torch.float32, device=dev)
-        argmax = torch.empty((B, 3, H), dtype=torch.int32, device=dev) if kind == 0 else None
-        _lib.check(lib.gcnpt_pool3_fwd(st, _lib.ptr(outs[-1]), _lib.dtype_code(outs[-1].dtype), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op), B, T, H, kind,
-                                       _lib.ptr(pooled), _lib.ptr(argmax)))
+        nb = trees.B                                              # sentences (B above is the row count on packed rows)
+        pooled = torch.empty((nb, 3 * H), dtype=torch.float32, device=dev)
+        argmax = torch.empty((nb, 3, H), dtype=torch.int32, device=dev) if kind == 0 else None
+        if getattr(trees, "packed", False):
+            # packed rows: the poolings read the stack's [N,H] rows where they lie (no unpack_rows, no [B,T,H] tensor)
+            _lib.check(lib.gcnpt_pool3_fwd_packed(st, _lib.ptr(outs[-1]), _lib.dtype_code(outs[-1].dtype), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op),
+                                                  _lib.ptr(trees.cu_seqlens), nb, trees.T, rows, H, kind, _lib.ptr(pooled), _lib.ptr(argmax)))
+        else:
+            _lib.check(lib.gcnpt_pool3_fwd(st, _lib.ptr(outs[-1]), _lib.dtype_code(outs[-1].dtype), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op), B, T, H, kind,
+                                           _lib.ptr(pooled), _lib.ptr(argmax)))
         ctx.save_for_backward(*outs, *wb, *(s_frag if need_w else []))
         ctx.pool = (pm, sp, op, argmax, kind)
         return pooled
@@ -186,9 +192,14 @@ class _GCNLayersFn(torch.autograd.Function):
             pm, sp, op, argmax, kind = pool
             H = dims[-1][0]
             g = torch.empty_like(outs[-1])                       # dZ of the top layer, straight from the pooling's backward
-            _lib.check(lib.gcnpt_pool3_bwd_dz(st, _lib.ptr(gout.to(torch.float32).contiguous()), _lib.ptr(argmax), _lib.ptr(pm), _lib.ptr(sp),
-                                              _lib.ptr(op), B, T, H, kind, _lib.ptr(outs[-1]), _lib.ptr(trees.ell), scales[-1], _lib.ptr(g),
-                                              _lib.dtype_code(g.dtype)))
+            g32 = gout.to(torch.float32).contiguous()
+            if getattr(trees, "packed", False):
+                _lib.check(lib.gcnpt_pool3_bwd_dz_packed(st, _lib.ptr(g32), _lib.ptr(argmax), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op),
+                                                         _lib.ptr(trees.cu_seqlens), trees.B, trees.T, ctx.rows, H, kind, _lib.ptr(outs[-1]),
+                                                         _lib.ptr(trees.ell), scales[-1], _lib.ptr(g), _lib.dtype_code(g.dtype)))
+            else:
+                _lib.check(lib.gcnpt_pool3_bwd_dz(st, _lib.ptr(g32), _lib.ptr(argmax), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op), B, T, H, kind,
+                                                  _lib.ptr(outs[-1]), _lib.ptr(trees.ell), scales[-1], _lib.ptr(g), _lib.dtype_code(g.dtype)))
         in_dtypes = [ctx.x_dtype if l == 0 else outs[l - 1].dtype for l in range(L)]
         dhs = [torch.empty(ctx.lead + (K,), dtype=in_dtypes[l], device=dev) if (l > 0 or ctx.needs_input_grad[0]) else None
                for l, (_, K) in enumerate(dims)]
@@ -216,8 +227,8 @@ class _GCNLayersFn(torch.autograd.Function):
 def gcn_layers(x, weights, biases, trees, drop_p=None, seeds=None, compute_dtype=torch.float32, out_dtype=torch.float32, no_adj=False,
                seed_dev=None, wcache=None, pool=None, prepacked=None, acts=None):
     """
-    The reference's whole layer loop (model/gcn.py:266-393) over the per-layer kernels.  x [B,T,Din] float32/bfloat16 CUDA;
-    weights / biases: lists of the nn.Linear parameters (any widths that chain); drop_p[l]: dropout applied to the output of
+    The reference's whole layer loop (model/gcn.py:266-393) over the per-layer kernels.  x [B,T,Din] float32/bfloat16 CUDA, or
+    token-packed rows [N,Din] with a PackedTrees; weights / biases: lists of the nn.Linear parameters (any widths that chain); drop_p[l]: dropout applied to the output of
     layer l (0 for the last); acts: None or a list that receives every layer's stored output; wcache: an empty dict the caller keeps -- the packed weight images are reused while the weights'
     version counters stand still; pool: see below.  compute_dtype float32 = exact fp32 MFMA (activations stay float32), bfloat16 = bf16 operands
     and bf16 activations between the layers, fp32 accumulation; the last layer's output has out_dtype.
@@ -234,10 +245,9 @@ def gcn_layers(x, weights, biases, trees, drop_p=None, seeds=None, compute_dtype
                seed_dev=seed_dev, wcache=wcache, pool=None, prepacked=prepacked, acts=acts)
     if pool is not None:
         # pool = (subj_pos, obj_pos, 'max' | 'avg' | 'sum'): the op returns float32 [B, 3H] = pool3(h_L, trees.pool_mask, subj_pos, obj_pos)
-        # instead of h_L (padded layout only)
-        if getattr(trees, "packed", False):
-            raise ValueError("gcn_layers(pool=...) needs the padded layout")
+        # instead of h_L; with a PackedTrees = pool3_packed(h_L, trees, subj_pos, obj_pos), the positions being the padded [B,T] tensors
         sp, op, kind = pool
+        _check_positions("gcn_layers(pool=...)", sp, op, trees)
         cfg["pool"] = (sp.contiguous(), op.contiguous(), 0 if kind == 'max' else (1 if kind == 'avg' else 2))
     params = [t for wb in zip(weights, biases) for t in wb]
     return _GCNLayersFn.apply(x, trees, cfg, *params)
@@ -400,9 +410,11 @@ class GCNRelationModel(nn.Module):
         return self._forward_trees(inputs, trees, pack, subj_pos, obj_pos)
 
     def _forward_trees(self, inputs, trees, pack, subj_pos, obj_pos):
-        # regular adjacency on the padded layout: the GCN returns the three pooled vectors itself (stack + pooling as ONE autograd op, so the
-        # pooling's backward hands the top layer its dZ); opt['gcn_pool_handover'] = False keeps the two ops apart
-        handover = (self.adj_type == 'regular' and isinstance(trees, (PrunedTrees, CompactTrees)) and self.opt.get('gcn_pool_handover', True))
+        # regular adjacency, padded or token-packed rows: the GCN returns the three pooled vectors itself (stack + pooling as ONE autograd op, so
+        # the pooling's backward hands the top layer its dZ; packed rows are pooled where they lie, never unpacked); opt['gcn_pool_handover'] =
+        # False keeps the two ops apart (packed: unpack_rows, then pool3 on [B,T,H])
+        handover = (self.adj_type == 'regular' and isinstance(trees, (PrunedTrees, CompactTrees, PackedTrees))
+                    and self.opt.get('gcn_pool_handover', True))
         if isinstance(trees, CompactTrees):
             # only the tokens of the pruned trees and the entity tokens are computed ([B,Tc,H]); the three poolings never look at
             # any other (gcn.py:116-119), so the pooled vectors are the full batch's
@@ -685,6 +697,11 @@ class GCN(nn.Module):
             xp = packed.pack_rows(gcn_inputs if gcn_inputs.dtype in (torch.float32, torch.bfloat16) else gcn_inputs.float())
             pre, self._prepacked = getattr(self, "_prepacked", None), None
             wcache = self._wcache if self._cache_usable() else None
+            req = getattr(self, "_pool_req", None)
+            if req is not None:
+                # the pooled vectors straight from the packed rows (as the padded branch below): the stack's output is never unpacked
+                return _Pooled(gcn_layers(xp, Ws, bs, packed, ps, seeds, self.compute_dtype, torch.float32, no_adj, seed_dev, wcache, pool=req,
+                                          prepacked=pre)), packed.padded.pool_mask
             hp = gcn_layers(xp, Ws, bs, packed, ps, seeds, self.compute_dtype, torch.float32, no_adj, seed_dev, wcache, prepacked=pre)
             return packed.unpack_rows(hp), packed.padded.pool_mask
         trees = adj if isinstance(adj, PrunedTrees) else adj_to_csr(adj, want_label=False)   # gcn.py:260-262
@@ -921,6 +938,63 @@ def pool3(h, pool_mask, subj_pos, obj_pos, type='max'):
         raise TypeError("pool3: pool_mask must be bool/uint8, subj_pos / obj_pos int64")
     kind = 0 if type == 'max' else (1 if type == 'avg' else 2)
     return _Pool3Fn.apply(h, pool_mask, subj_pos, obj_pos, kind)
+
+
+def _check_positions(what, subj_pos, obj_pos, trees):
+    """The position tensors of a pooling over `trees`' batch: the loader's padded int64 [B,T], whatever layout the rows have."""
+    for name, t in (("subj_pos", subj_pos), ("obj_pos", obj_pos)):
+        if t.dtype != torch.int64 or tuple(t.shape) != (trees.B, trees.T):
+            raise TypeError("%s: %s must be int64 [%d,%d], got %s %s" % (what, name, trees.B, trees.T, t.dtype, tuple(t.shape)))
+
+
+class _Pool3PackedFn(torch.autograd.Function):
+    """_Pool3Fn on token-packed rows (gcnpt_pool3_fwd_packed / gcnpt_pool3_bwd_packed): sentence b pools rows cu_seqlens[b] .. cu_seqlens[b+1]-1."""
+
+    @staticmethod
+    def forward(ctx, h, trees, subj_pos, obj_pos, kind):
+        N, H = h.shape
+        lib, st = _lib.lib(), _lib.stream()
+        h = h.contiguous()
+        pm = trees.pool_mask.contiguous()
+        sp, op = subj_pos.contiguous(), obj_pos.contiguous()
+        out = torch.empty((trees.B, 3 * H), dtype=torch.float32, device=h.device)
+        argmax = torch.empty((trees.B, 3, H), dtype=torch.int32, device=h.device) if kind == 0 else None
+        _lib.check(lib.gcnpt_pool3_fwd_packed(st, _lib.ptr(h), _lib.dtype_code(h.dtype), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op),
+                                              _lib.ptr(trees.cu_seqlens), trees.B, trees.T, N, H, kind, _lib.ptr(out), _lib.ptr(argmax)))
+        ctx.save_for_backward(pm, sp, op, argmax)
+        ctx.kind, ctx.shape, ctx.h_dtype, ctx.trees = kind, (N, H), h.dtype, trees
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pm, sp, op, argmax = ctx.saved_tensors
+        N, H = ctx.shape
+        trees = ctx.trees
+        dh = torch.empty((N, H), dtype=ctx.h_dtype, device=g.device)
+        g = g.to(torch.float32).contiguous()
+        _lib.check(_lib.lib().gcnpt_pool3_bwd_packed(_lib.stream(), _lib.ptr(g), _lib.ptr(argmax), _lib.ptr(pm), _lib.ptr(sp), _lib.ptr(op),
+                                                     _lib.ptr(trees.cu_seqlens), trees.B, trees.T, N, H, ctx.kind, _lib.ptr(dh),
+                                                     _lib.dtype_code(ctx.h_dtype)))
+        return dh, None, None, None, None
+
+
+def pool3_packed(h, trees, subj_pos, obj_pos, type='max'):
+    """
+    pool3 on token-packed rows: h [N,H] float32/bfloat16 CUDA (N = trees.N rows, sentence b's token i at row cu_seqlens[b] + i), trees a
+    PackedTrees (its pool_mask [N,1] is the tree mask), subj_pos / obj_pos the loader's padded int64 [B,T].  Returns float32 [B, 3H];
+    differentiable (the gradient of h is written completely, rows past sum(len) as zeros).
+    Equal to pool3(trees.unpack_rows(h), <padded pool mask>, subj_pos, obj_pos) bit for bit when every pad slot of the positions is
+    non-zero, which is what the loader writes (150, data/loader.py:120-121): a pad slot with position 0 is a subject / object token of
+    value zero in the padded form and does not exist in the packed form.
+    """
+    if not isinstance(trees, PackedTrees):
+        raise TypeError("pool3_packed: trees must be a PackedTrees (PrunedTrees.pack, prune_to_csr_packed, TreeCache.batch_packed)")
+    _lib.require_gpu(h)
+    if h.dim() != 2 or h.shape[0] != trees.N:
+        raise RuntimeError("pool3_packed: packed trees hold %d rows but h is %s" % (trees.N, tuple(h.shape)))
+    _check_positions("pool3_packed", subj_pos, obj_pos, trees)
+    kind = 0 if type == 'max' else (1 if type == 'avg' else 2)
+    return _Pool3PackedFn.apply(h, trees, subj_pos, obj_pos, kind)
 
 
 def pool(h, mask, type='max'):

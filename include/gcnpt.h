@@ -317,7 +317,7 @@ int gcnpt_layers_step(void* stream, const gcnpt_step_t* step);
  *   either is too small (nothing usable is written then), [1] = sum(len) seen.
  * EVERY layer entry point above takes the packed form with T = 0: then `B` is the number of packed rows N, the pattern's
  * columns are absolute row numbers and row_ptr has N+1 entries (gcnpt_layer_fwd, gcnpt_layer_bwd_data, gcnpt_layer_bwd_weight[_multi],
- * gcnpt_layers_fwd, gcnpt_layers_bwd; fragment images: gcnpt_frag_bytes(N, width, dtype)).  Rows keep their values: a packed row
+ * gcnpt_layers_fwd, gcnpt_layers_bwd, gcnpt_layers_bwd_dz; fragment images: gcnpt_frag_bytes(N, width, dtype)).  Rows keep their values: a packed row
  * is bit-identical to the same token's row of the padded batch.
  * gcnpt_pack_rows: src [B*T, W] -> dst [N, W] (dst[cu[b]+i] = src[b*T+i], i < len[b]); gcnpt_unpack_rows: the inverse, slots past a
  * sentence's end are zero-filled (the reference leaves relu(pad-row . W + 2b) there; every consumer masks those slots,
@@ -383,6 +383,19 @@ int gcnpt_pool3_fwd(void* stream, const void* h, int h_dtype, const uint8_t* poo
                     const int64_t* obj_pos, int B, int T, int H, int type, float* out, int32_t* argmax);
 int gcnpt_pool3_bwd(void* stream, const float* g, const int32_t* argmax, const uint8_t* pool_mask, const int64_t* subj_pos,
                     const int64_t* obj_pos, int B, int T, int H, int type, void* dh, int dh_dtype);
+/* The same poolings on TOKEN-PACKED rows (model/gcn.py:116-121 + pool() 473-483 over the rows gcnpt_pack_trees describes): sentence b
+ * pools the rows cu_seqlens[b] .. cu_seqlens[b+1]-1 of h [n_rows,H] -- the layer stack's output where it lies, no [B,T,H] copy -- with
+ * pool_mask uint8 [n_rows] read at the same row.  subj_pos / obj_pos stay the loader's padded int64 [B*T] tensors (data/loader.py:120-121),
+ * read at b*T + i; a sentence pools at most T tokens.  out [B,3H] and argmax [B,3,H] (the sentence-local token i) equal the padded entry
+ * points' bit for bit where every pad slot of subj_pos / obj_pos is non-zero, as the loader writes them (a pad slot with position 0 is a
+ * subject token of value zero in the padded form and does not exist here).  A sentence without rows gives -1e12 (max), 0 (sum), 0/0 (avg).
+ * gcnpt_pool3_bwd_packed writes dh [n_rows,H] completely: rows from cu_seqlens[B] on (n_rows may exceed sum(len)) are zeroed. */
+int gcnpt_pool3_fwd_packed(void* stream, const void* h, int h_dtype, const uint8_t* pool_mask, const int64_t* subj_pos,
+                           const int64_t* obj_pos, const int32_t* cu_seqlens, int B, int T, int n_rows, int H, int type, float* out,
+                           int32_t* argmax);
+int gcnpt_pool3_bwd_packed(void* stream, const float* g, const int32_t* argmax, const uint8_t* pool_mask, const int64_t* subj_pos,
+                           const int64_t* obj_pos, const int32_t* cu_seqlens, int B, int T, int n_rows, int H, int type, void* dh,
+                           int dh_dtype);
 /* Hand-over from the pooling to the layer stack (model/gcn.py:114-121: the pooled tensor IS the top GCN layer's output): instead of dh
  * the pooling's backward leaves dz = dh * 1[y > 0] * scale / (deg + 1), i.e. dZ of that layer (gcn.py:390-393 differentiated), with y
  * [dev] [B*T,H] = the layer's stored output (same dtype as dz), ell = the forward pattern's ELL head (degrees), scale = 1/(1-p) of the
@@ -391,6 +404,12 @@ int gcnpt_pool3_bwd(void* stream, const float* g, const int32_t* argmax, const u
 int gcnpt_pool3_bwd_dz(void* stream, const float* g, const int32_t* argmax, const uint8_t* pool_mask, const int64_t* subj_pos,
                        const int64_t* obj_pos, int B, int T, int H, int type, const void* y, const int32_t* ell, float scale, void* dz,
                        int dtype);
+/* The hand-over on token-packed rows (model/gcn.py:114-121, 390-393 as above): y and dz are [n_rows,H], ell the PACKED forward ELL head
+ * int32 [n_rows*8]; rows from cu_seqlens[B] on are zeroed, so the weight gradient may contract over all n_rows rows of the dZ image.
+ * gcnpt_layers_bwd_dz then takes it in the packed form (T = 0, B = n_rows). */
+int gcnpt_pool3_bwd_dz_packed(void* stream, const float* g, const int32_t* argmax, const uint8_t* pool_mask, const int64_t* subj_pos,
+                              const int64_t* obj_pos, const int32_t* cu_seqlens, int B, int T, int n_rows, int H, int type, const void* y,
+                              const int32_t* ell, float scale, void* dz, int dtype);
 int gcnpt_layers_bwd_dz(void* stream, int n_layers, const void* dz_top, const void* const* Y, const int* y_dtype,
                         const void* const* w_bwd, const int32_t* ell, const int32_t* rowT_ptr, const int32_t* colT_idx,
                         const int32_t* ellT, int B, int T, const int* Din, const int* H, void* const* dh, const int* dh_dtype,
