@@ -88,6 +88,8 @@ SIGNATURES = {
     "gcnpt_bilinear_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p, _i]),
     "gcnpt_lstm_fwd": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "gcnpt_lstm_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "gcnpt_embed_fwd": (_i, [_p] * 8 + [_i] * 6 + [_p, _i, _i, _i, _p, _i, _f, _f, _u64, _u64, _p, _p]),
+    "gcnpt_embed_bwd": (_i, [_p, _p, _i, _p, _p, _p] + [_i] * 6 + [_p, _i, _i, _i, _f, _f, _u64, _u64, _p, _i, _i] + [_p] * 5),
 }
 
 

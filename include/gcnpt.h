@@ -539,6 +539,43 @@ int gcnpt_full_agg_bwd(void* stream, const float* dy, const float* y, const int3
                        const int32_t* label, const uint8_t* keep_f, const uint8_t* keep_r, int B, int T, int H, int M, float scale,
                        float* dagg, float* dyf, float* dyr);
 
+/* ---- the embedding front end, model/gcn.py:235-241 (+ EmbeddingDropout, model/dropouts.py:23-39): the layer stack's input in ONE launch ----
+ *   out[row] = in_drop([emb_drop(emb[words]) | pos_emb[pos] | ner_emb[ner]]),  width Din = E0 + E1 + E2
+ * words / pos / ner [dev] int64 [B*T] (the loader's padded id tensors); emb [V0,E0], pos_emb [V1,E1], ner_emb [V2,E2] [dev] float32 tables.
+ * E1 = 0 / E2 = 0: no such segment (its pointers are unused).  Instead of `words` + `emb` the word segment may come from a dense source
+ * word_dense [dev] float32 [B*T,E0] (the reference's BERT case, gcn.py:235-236): exactly one of `words`, `word_dense` is given, and the
+ * word-type dropout does not apply to a dense source.
+ * Layout of `out` (out_dtype: GCNPT_F32, or GCNPT_BF16 = round to nearest even): cu_seqlens NULL = padded [B*T,Din], EVERY slot written as
+ * the ids say, pad slots included; cu_seqlens [dev] int32 [B+1] (gcnpt_pack_trees) = token-packed [n_rows,Din], only tokens
+ * i < min(cu[b+1]-cu[b], T) of sentence b are written, at row cu[b]+i (rows outside [0,n_rows) are never touched) -- gcnpt_pack_rows of
+ * the padded output, bit for bit, under dropout too.
+ * Dropout (the counter-based hash of the layer kernels, 16-bit thresholds; seed_dev [dev] NULL or a uint64 word added to both seeds, for
+ * fresh masks on every replay of a captured graph):
+ *   p_emb  word-type dropout: ONE decision per (sentence b, word id), keyed on (seed_emb, b, id) -- every occurrence of a word in a
+ *          sentence is kept or dropped together, as the reference's [B,V] Bernoulli matrix + gather do; word segment only
+ *   p_in   element dropout of the whole row, keyed on (seed_in, b*T + t, column): the padded token number in both layouts
+ *   out = (v * s_emb) * s_in in float32 with s = 1/(1-p) computed in float32 (s_emb = 1 outside the word segment); a dropped element is +0.0.
+ * An id outside its table reads nothing: its segment is zero, gets no gradient, and status [dev] int32 [1] (optional; cleared by the call
+ * on the stream first) receives bit 0 (word), 1 (POS) or 2 (NER).
+ * gcnpt_embed_bwd: ONE launch over g [dev] (g_dtype; the layout `out` had) that recomputes the keep decisions from the same seeds -- no
+ * mask is stored.  Every output is optional (at least one must be given); accumulators are cleared by the call on the stream first:
+ *   d_emb       float32 [V0,E0]   dense form: float atomic adds, one wave per token row, 256 contiguous bytes per wave-instruction
+ *   d_emb_rows  float32 [B*T,E0]  row-sparse form (not together with d_emb): token n's masked gradient row, plain stores, written completely
+ *               -- the values of a sparse_coo_tensor whose indices are the flattened `words`
+ *   d_word_dense float32 [B*T,E0] gradient of a dense word source (words == NULL), plain masked stores, written completely
+ *   d_pos_emb [V1,E1], d_ner_emb [V2,E2]  float32: each workgroup sums its tokens in LDS and adds only the table rows it touched
+ * A token whose word id equals padding_idx (< 0: none), is >= topn (<= 0 or >= V0: no limit; gcn.py:84-88), is out of range, or whose word
+ * type was dropped issues no atomic on the word table; the row-sparse form holds a zero row for it.  On the packed layout the slots past
+ * each sentence's end contribute nothing (zero rows in the plain-store forms). */
+int gcnpt_embed_fwd(void* stream, const int64_t* words, const float* word_dense, const int64_t* pos, const int64_t* ner, const float* emb,
+                    const float* pos_emb, const float* ner_emb, int V0, int V1, int V2, int E0, int E1, int E2, const int32_t* cu_seqlens,
+                    int B, int T, int n_rows, void* out, int out_dtype, float p_emb, float p_in, uint64_t seed_emb, uint64_t seed_in,
+                    const uint64_t* seed_dev, int32_t* status);
+int gcnpt_embed_bwd(void* stream, const void* g, int g_dtype, const int64_t* words, const int64_t* pos, const int64_t* ner, int V0, int V1,
+                    int V2, int E0, int E1, int E2, const int32_t* cu_seqlens, int B, int T, int n_rows, float p_emb, float p_in,
+                    uint64_t seed_emb, uint64_t seed_in, const uint64_t* seed_dev, int padding_idx, int topn, float* d_emb,
+                    float* d_emb_rows, float* d_word_dense, float* d_pos_emb, float* d_ner_emb);
+
 #ifdef __cplusplus
 }
 #endif

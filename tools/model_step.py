@@ -6,7 +6,11 @@ weights; eager launches (ctypes + torch), one optimizer-free fwd+bwd per step.  
   C2: GCNClassifier, 2-layer GCN, no LSTM, B=50 T=100 hidden=200 (emb 300 + pos 30 + ner 30)
   C3: the same with the BiLSTM in front (rnn_hidden 200), i.e. C-GCN; C3_cgcn_native_rnn: its BiLSTM on the native recurrence
       (opt['gcn_native_rnn'], model/rnn.py) instead of MIOpen's
+  *_native_embed: the same cell with opt['gcn_native_embed'] (lookups, cat, dropouts, cast as one launch; csrc/embed_kernels.hip).
+      Every cell has emb_dropout = 0, so neither front end runs its word-type dropout here: input_dropout = 0.5 is what both pay for
+--cells A,B: only the named cells (C2_gcn, C2_gcn_native_embed, C3_cgcn, ...); --no-copy: skip the copy bandwidth measurement
 """
+import argparse
 import json
 import os
 import sys
@@ -20,14 +24,19 @@ from gcn_over_pruned_trees_amd.model import gcn, tree  # noqa: E402
 from gcn_over_pruned_trees_amd.utils import synthetic  # noqa: E402
 
 
-def opt_for(rnn, dtype, native_rnn=False):
+def opt_for(rnn, dtype, native_rnn=False, native_embed=False):
     return dict(vocab_size=5000, emb_dim=300, pos_dim=30, ner_dim=30, hidden_dim=200, num_layers=2, input_dropout=0.5, gcn_dropout=0.5,
                 word_dropout=0.04, emb_dropout=0.0, topn=1e10, prune_k=1, pooling="max", pooling_l2=0.003, mlp_layers=2, no_adj=False,
                 rnn=rnn, rnn_hidden=200, rnn_layers=1, rnn_dropout=0.5, cuda=True, dataset="tacred", num_class=42, adj_type="regular",
-                gcn_dtype=dtype, gcn_check_trees=False, gcn_native_rnn=native_rnn)
+                gcn_dtype=dtype, gcn_check_trees=False, gcn_native_rnn=native_rnn, gcn_native_embed=native_embed)
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", default="")
+    ap.add_argument("--no-copy", action="store_true")
+    args = ap.parse_args()
+    only = [c for c in args.cells.split(",") if c]
     dev = torch.device("cuda:0")
     B, T = 50, 100
     tb = synthetic.random_tree_batch(1236, B, T, "tacred")
@@ -39,10 +48,13 @@ def main():
               t(tb["deprel"]), t(tb["head"]), t(tb["subj_pos"]), t(tb["obj_pos"]))
     labels = t(rng.randint(0, 42, size=(B,)).astype(np.int64))
     out = {}
-    for name, rnn, native in (("C2_gcn", False, False), ("C3_cgcn", True, False), ("C3_cgcn_native_rnn", True, True)):
+    for name, rnn, native, embed in (("C2_gcn", False, False, False), ("C2_gcn_native_embed", False, False, True), ("C3_cgcn", True, False, False),
+                                     ("C3_cgcn_native_rnn", True, True, False), ("C3_cgcn_native_rnn_native_embed", True, True, True)):
+        if only and name not in only:
+            continue
         for dtype in ("fp32", "bf16"):
             torch.manual_seed(1234)
-            model = gcn.GCNClassifier(opt_for(rnn, dtype, native)).to(dev).train()
+            model = gcn.GCNClassifier(opt_for(rnn, dtype, native, embed)).to(dev).train()
             cache = tree.TreeCache.build(inputs[5], inputs[6], inputs[7], inputs[4], 1, masks=inputs[1], want_label=False)
             idx = torch.arange(B, device=dev)
 
@@ -64,6 +76,9 @@ def main():
                 dt = (time.perf_counter() - t0) / n
                 out["%s_%s_%s" % (name, dtype, "cached_trees" if cached else "pruned_in_step")] = dict(
                     ms_per_step=round(dt * 1e3, 3), sentences_per_s=round(B / dt), loss=float(loss))
+    if args.no_copy:
+        print(json.dumps(out))
+        return
     # device copy bandwidth: 1 GiB read + 1 GiB write per copy
     a = torch.empty((1 << 28,), dtype=torch.float32, device=dev)
     b = torch.empty_like(a)
