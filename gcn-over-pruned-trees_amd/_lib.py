@@ -162,6 +162,11 @@ def ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 
 
+def int_array(values):
+    """Host int array for the entry points that take one int per layer."""
+    return (ctypes.c_int * len(values))(*values)
+
+
 def stream():
     import torch
     return torch.cuda.current_stream().cuda_stream

@@ -1,0 +1,185 @@
+"""
+The ops of the relation-aware adjacency types: `full_deprel`'s fused aggregation and bilinear traversal (reference model/gcn.py:296-388,
+400-434; csrc/full_kernels.hip, csrc/bilinear_kernels.hip) and the `diagonal_deprel` layer (gcn.py:272-294; csrc/diag_kernels.hip).
+"""
+import torch
+
+from .. import _lib
+from ..utils import constant
+
+
+class _FullAggFn(torch.autograd.Function):
+    """Aggregation + self loop + /(deg+1) + ReLU + dropout of a full_deprel layer in one kernel (csrc/full_kernels.hip); reference
+    model/gcn.py:308-311, 331, 340-344, 362, 385, 390-393."""
+
+    @staticmethod
+    def forward(ctx, yf, yr, self_term, trees, pos, keep_f, keep_r, M, drop_p, seed, seed_dev):
+        B, T = trees.B, trees.T
+        H = yf.shape[1]
+        P = _lib.ptr
+        yf = yf.to(torch.float32).contiguous()
+        yr = yr.to(torch.float32).contiguous() if yr is not None else None
+        st = self_term.to(torch.float32).contiguous() if self_term is not None else None
+        out = torch.empty((B * T, H), dtype=torch.float32, device=yf.device)
+        _lib.check(_lib.lib().gcnpt_full_agg_fwd(_lib.stream(), P(yf), P(yr), P(st), P(pos), P(trees.row_ptr), P(trees.col_idx), P(trees.label),
+                                                 P(keep_f), P(keep_r), B, T, H, int(M), P(out), float(drop_p), int(seed), P(seed_dev)))
+        ctx.save_for_backward(out, pos, keep_f, keep_r)
+        ctx.trees, ctx.M, ctx.rows = trees, int(M), (yf.shape[0], yr is not None, st is not None)
+        ctx.scale = 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, pos, keep_f, keep_r = ctx.saved_tensors
+        trees = ctx.trees
+        B, T, H = trees.B, trees.T, out.shape[1]
+        rows, has_r, has_self = ctx.rows
+        P = _lib.ptr
+        g = g.to(torch.float32).contiguous()
+        dagg = torch.empty_like(out)
+        dyf = torch.zeros((rows, H), dtype=torch.float32, device=out.device)
+        dyr = torch.zeros((rows, H), dtype=torch.float32, device=out.device) if has_r else None
+        _lib.check(_lib.lib().gcnpt_full_agg_bwd(_lib.stream(), P(g), P(out), P(pos), P(trees.row_ptr), P(trees.col_idx), P(trees.label),
+                                                 P(keep_f), P(keep_r), B, T, H, ctx.M, ctx.scale, P(dagg), P(dyf), P(dyr)))
+        return dyf, dyr, (dagg if has_self else None), None, None, None, None, None, None, None, None
+
+
+class _BilinearFn(torch.autograd.Function):
+    """y = sum_d e[:,d] * (x @ W3[d]) + e @ b3 (reference traverse_deprel, model/gcn.py:400-415) with the contraction on
+    csrc/bilinear_kernels.hip in either precision: exact fp32 MFMA (the module's default) or bf16 operands with fp32 accumulation.
+    The outer product e (x) x the reference materialises never exists.  The op is linear in each argument: dx is the same kernel on
+    the transposed weight image, de the same per-relation products dotted with the upstream gradient, dW the token contraction
+    of row-contraction fragment images with the gy fragments scaled by e in registers (gcnpt_bilinear_bwd_w)."""
+
+    @staticmethod
+    def forward(ctx, xt, e, weight, bias, compute):
+        M, Tin = xt.shape
+        D = e.shape[1]
+        H = weight.shape[0] // D
+        lib, st, dev = _lib.lib(), _lib.stream(), xt.device
+        k = 32 if compute == _lib.BF16 else 16
+        op_dtype = torch.bfloat16 if compute == _lib.BF16 else torch.float32
+        w32 = weight.detach().to(torch.float32).contiguous()
+        img = torch.empty((lib.gcnpt_bilinear_packed_bytes(D, Tin, H, compute),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.gcnpt_bilinear_pack(st, _lib.ptr(w32), D, Tin, H, _lib.ptr(img), 0, compute))
+        xb = torch.zeros((M, (Tin + k - 1) // k * k), dtype=op_dtype, device=dev)
+        xb[:, :Tin] = xt.detach()
+        e32 = e.detach().to(torch.float32).contiguous()
+        planes = torch.empty((lib.gcnpt_bilinear_planes(M, D, Tin, H, compute), M, H), dtype=torch.float32, device=dev)
+        _lib.check(lib.gcnpt_bilinear_fwd(st, _lib.ptr(xb), _lib.ptr(e32), _lib.ptr(img), M, D, Tin, H, _lib.ptr(planes), compute))
+        y = torch.addmm(planes.sum(0), e32, bias.detach().to(torch.float32).reshape(D, H))      # + e @ b3, gcn.py:413
+        ctx.save_for_backward(xt, e, weight, bias, xb, img)
+        ctx.compute = compute
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xt, e, weight, bias, xb, img = ctx.saved_tensors
+        compute = ctx.compute
+        M, Tin = xt.shape
+        D = e.shape[1]
+        H = weight.shape[0] // D
+        lib, st, dev = _lib.lib(), _lib.stream(), xt.device
+        k = 32 if compute == _lib.BF16 else 16
+        op_dtype = torch.bfloat16 if compute == _lib.BF16 else torch.float32
+        gy = gy.to(torch.float32).contiguous()
+        x32, e32 = xt.to(torch.float32), e.to(torch.float32).contiguous()
+        w32 = weight.detach().to(torch.float32).contiguous()
+        b3 = bias.to(torch.float32).reshape(D, H)
+        dx = de = dW = db = None
+        on_kernel = bool(lib.gcnpt_bilinear_supported(D, H, Tin, compute))         # the transposed problem contracts over H
+        if ctx.needs_input_grad[0]:
+            if on_kernel:       # dx = sum_d e_d (gy @ W3[d]^T): the forward kernel on the transposed weight image
+                imgT = torch.empty((lib.gcnpt_bilinear_packed_bytes(D, H, Tin, compute),), dtype=torch.uint8, device=dev)
+                _lib.check(lib.gcnpt_bilinear_pack(st, _lib.ptr(w32), D, Tin, H, _lib.ptr(imgT), 1, compute))
+                gyb = torch.zeros((M, (H + k - 1) // k * k), dtype=op_dtype, device=dev)
+                gyb[:, :H] = gy
+                planes = torch.empty((lib.gcnpt_bilinear_planes(M, D, H, Tin, compute), M, Tin), dtype=torch.float32, device=dev)
+                _lib.check(lib.gcnpt_bilinear_fwd(st, _lib.ptr(gyb), _lib.ptr(e32), _lib.ptr(imgT), M, D, H, Tin, _lib.ptr(planes), compute))
+                dx = planes.sum(0)
+            else:
+                dx = (torch.mm(gy, w32.reshape(D * Tin, H).t()).view(M, D, Tin) * e32.unsqueeze(2)).sum(1)
+        if ctx.needs_input_grad[1]:
+            # de[m,d] = (x[m] @ W3[d]) . gy[m] + gy[m] . b3[d]: the forward's per-relation products, dotted instead of summed
+            planes = torch.empty((lib.gcnpt_bilinear_de_planes(M, D, Tin, H, compute), M, D), dtype=torch.float32, device=dev)
+            _lib.check(lib.gcnpt_bilinear_bwd_e(st, _lib.ptr(xb), _lib.ptr(gy), _lib.ptr(img), M, D, Tin, H, _lib.ptr(planes), compute))
+            de = torch.addmm(planes.sum(0), gy, b3.t())
+        if ctx.needs_input_grad[2]:                                       # dW3[d] = (e_d * x)^T gy without the [M, D*Tin] outer product
+            u8 = dict(dtype=torch.uint8, device=dev)
+            xI = torch.empty((lib.gcnpt_rows_image_bytes(M, Tin, compute),), **u8)
+            gI = torch.empty((lib.gcnpt_rows_image_bytes(M, H, compute),), **u8)
+            x32c = x32.contiguous()
+            _lib.check(lib.gcnpt_rows_pack(st, _lib.ptr(x32c), M, Tin, _lib.ptr(xI), compute))
+            _lib.check(lib.gcnpt_rows_pack(st, _lib.ptr(gy), M, H, _lib.ptr(gI), compute))
+            eT = torch.zeros((D, (M + k - 1) // k * k), dtype=torch.float32, device=dev)
+            eT[:, :M] = e32.t()
+            dW32 = torch.empty(weight.shape, dtype=torch.float32, device=dev)
+            _lib.check(lib.gcnpt_bilinear_bwd_w(st, _lib.ptr(xI), _lib.ptr(gI), _lib.ptr(eT), M, D, Tin, H, _lib.ptr(dW32), compute))
+            dW = dW32.to(weight.dtype)
+        if ctx.needs_input_grad[3]:
+            db = torch.mm(e32.t(), gy).reshape(-1).to(bias.dtype)
+        return dx, de, dW, db, None
+
+
+def bilinear_traverse(xt, e, weight, bias, compute_dtype=torch.bfloat16):
+    """traverse_deprel of the reference for M compacted token rows: xt [M,Tin], e [M,D] relation vectors, weight [D*H,Tin] and
+    bias [D*H] of the shared nn.Linear (read as W3 [D,Tin,H] / b3 [D,H], gcn.py:301-303).  float32 [M,H].  compute_dtype: float32 =
+    exact fp32 MFMA, bfloat16 = bf16 operands with fp32 accumulation."""
+    for t in (xt, e, weight, bias):
+        _lib.require_gpu(t)
+    return _BilinearFn.apply(xt, e, weight, bias, _lib.dtype_code(compute_dtype))
+
+
+def bilinear_supported(D, Tin, H, compute_dtype=torch.bfloat16):
+    return bool(_lib.lib().gcnpt_bilinear_supported(int(D), int(Tin), int(H), _lib.dtype_code(compute_dtype)))
+
+
+def _zero_pad_row(grad):
+    grad = grad.clone()
+    grad[0].zero_()
+    return grad
+
+
+class _DiagLayerFn(torch.autograd.Function):
+    """One diagonal_deprel layer (csrc/diag_kernels.hip): reference model/gcn.py:272-294 + 390-393."""
+
+    @staticmethod
+    def forward(ctx, h, emb, deprel, trees, drop_p, seed, seed_dev=None):
+        for t in (h, emb, deprel):
+            _lib.require_gpu(t)
+        if trees.label is None:
+            raise ValueError("diagonal_deprel needs the adjacency values: build the trees with want_label=True")
+        B, T = trees.B, trees.T
+        H = h.shape[-1]
+        if h.shape[0] * h.shape[1] != B * T or emb.shape != (constant.N_DEPREL, H) or deprel.numel() != B * T:
+            raise ValueError("diag layer: h %s, table %s, deprel %s do not fit %d x %d trees" %
+                             (tuple(h.shape), tuple(emb.shape), tuple(deprel.shape), B, T))
+        h = h.contiguous()
+        E = emb.detach().float().contiguous()
+        deprel = deprel.contiguous()
+        out = torch.empty_like(h)
+        _lib.check(_lib.lib().gcnpt_diag_layer_fwd(_lib.stream(), _lib.ptr(h), _lib.dtype_code(h.dtype), _lib.ptr(E), _lib.ptr(deprel),
+                                                   _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx), _lib.ptr(trees.label), B, T, H,
+                                                   _lib.ptr(out), float(drop_p), int(seed), _lib.ptr(seed_dev)))
+        ctx.trees, ctx.scale = trees, (1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0)
+        ctx.save_for_backward(h, out, E, deprel)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        h, out, E, deprel = ctx.saved_tensors
+        trees = ctx.trees
+        B, T, H = trees.B, trees.T, h.shape[-1]
+        gout = gout.to(h.dtype).contiguous()
+        dh = torch.empty_like(h)
+        dE = torch.zeros_like(E)
+        _lib.check(_lib.lib().gcnpt_diag_layer_bwd(_lib.stream(), _lib.ptr(gout), _lib.ptr(out), _lib.ptr(h), _lib.dtype_code(h.dtype),
+                                                   _lib.ptr(E), _lib.ptr(deprel), _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx),
+                                                   _lib.ptr(trees.label), _lib.ptr(trees.rowT_ptr), _lib.ptr(trees.colT_idx), B, T, H,
+                                                   _lib.ptr(dh), _lib.ptr(dE), ctx.scale))
+        return dh, dE, None, None, None, None, None
+
+
+def diag_layer(h, deprel_table, deprel, trees, drop_p=0.0, seed=0, seed_dev=None):
+    """dropout(relu(((F (E[deprel] * h)) + (R (E[deprel+42] * h)) + E[84] * h) / (deg + 1))) for h [B,T,H] (fp32 or bf16)."""
+    return _DiagLayerFn.apply(h, deprel_table, deprel, trees, drop_p, seed, seed_dev)

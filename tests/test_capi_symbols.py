@@ -101,6 +101,9 @@ def test_host_mirror_keeps_reference_surface():
     assert list(inspect.signature(gcn.GCN.__init__).parameters) == ["self", "opt", "embeddings", "mem_dim", "num_layers"]
     assert list(inspect.signature(gcn.GCN.forward).parameters) == ["self", "adj", "inputs"]
     assert list(inspect.signature(gcn.pool).parameters) == ["h", "mask", "type"]
+    for name in ("gcn_layer", "gcn_layers", "gcn_layers_with_acts", "WeightPack", "embed_inputs", "_embed", "_EmbedFn", "pool", "pool3",
+                 "pool3_packed", "diag_layer", "_DiagLayerFn", "_FullAggFn", "bilinear_traverse", "bilinear_supported", "_Pooled"):
+        assert hasattr(gcn, name), name             # the ops live in their own modules; model.gcn keeps every name callers reach
     opt = dict(vocab_size=50, emb_dim=8, pos_dim=2, ner_dim=2, hidden_dim=16, num_layers=2, input_dropout=0.0, gcn_dropout=0.5,
                prune_k=1, pooling="max", mlp_layers=2, rnn=True, rnn_hidden=4, rnn_layers=1, rnn_dropout=0.0, dataset="tacred",
                num_class=42, topn=10, cuda=False)
