@@ -17,6 +17,7 @@ OK, E_INVALID, E_PRUNE_NEGATIVE, E_NO_SUBJECT, E_NO_LCA, E_CYCLE, E_BAD_HEAD, E_
 
 # every symbol include/gcnpt.h declares: (restype, argtypes)
 _p, _i, _f, _u64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
+_ll = ctypes.c_longlong
 
 
 class Step(ctypes.Structure):
@@ -90,6 +91,10 @@ SIGNATURES = {
     "gcnpt_lstm_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p]),
     "gcnpt_embed_fwd": (_i, [_p] * 8 + [_i] * 6 + [_p, _i, _i, _i, _p, _i, _f, _f, _u64, _u64, _p, _p]),
     "gcnpt_embed_bwd": (_i, [_p, _p, _i, _p, _p, _p] + [_i] * 6 + [_p, _i, _i, _i, _f, _f, _u64, _u64, _p, _i, _i] + [_p] * 5),
+    "gcnpt_head_linear_fwd": (_i, [_p, _p, _ll, _p, _p, _p, _i, _i, _i, _i]),
+    "gcnpt_head_linear_bwd": (_i, [_p, _p, _p, _p, _ll, _p, _p, _ll, _p, _p, _i, _i, _i, _i]),
+    "gcnpt_head_loss_fwd": (_i, [_p, _p, _p, _p, _ll, _i, _f, _i, _i, _p, _p, _p, _p]),
+    "gcnpt_head_loss_bwd": (_i, [_p, _p, _p, _p, _p, _ll, _i, _f, _i, _i, _p, _p]),
 }
 
 

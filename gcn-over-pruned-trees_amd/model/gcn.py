@@ -12,8 +12,9 @@ signatures as the reference, so `from model.gcn import GCNClassifier` can be swa
 
 What is different underneath: the tree pruning + adjacency build (gcn.py:96-110) is one device kernel
 (model/tree.py here) and every iteration of the layer loop (gcn.py:266-393) is one fused HIP kernel per
-direction, reached through the C-ABI of include/gcnpt.h.  Embeddings, pooling and the output MLP stay ordinary
-PyTorch-ROCm modules, as in the reference; so does the optional BiLSTM unless opt['gcn_native_rnn'] is set.
+direction, reached through the C-ABI of include/gcnpt.h.  Embeddings and the output MLP / classifier stay ordinary
+PyTorch-ROCm modules, as in the reference, unless opt['gcn_native_embed'] / opt['gcn_native_head'] is set; so does the optional
+BiLSTM unless opt['gcn_native_rnn'] is set.
 
 New optional `opt` keys (defaults reproduce the reference): `gcn_dtype` = 'fp32' | 'bf16' (MFMA operand /
 activation storage type inside the layer stack), `gcn_check_trees` = True (synchronise once per forward to
@@ -30,15 +31,22 @@ it is (tests/test_gpu_parity.py::test_training_step_graph_capture), the C-GCN mo
 `gcn_native_embed` = False (True: the embedding front end of GCN.forward -- the three lookups, the cat, word-type and input dropout, the bf16
 cast and, on PackedTrees, pack_rows -- is one launch forward and one backward, `embed_inputs` over csrc/embed_kernels.hip; the nn.Embedding
 modules keep the tables).
+`gcn_native_head` = False (True: out_mlp's Linear + ReLU layers and the classifier run as `linear_act`, and the new methods
+GCNClassifier.loss / GCNClassifier.predict -- the trainer's CrossEntropyLoss + pooling_l2 penalty and its softmax + argmax, reference
+model/trainer.py:94-100, 119-120 -- as `head_loss` / `head_predict`, one launch per op and direction over csrc/head_kernels.hip; the
+nn.Linear modules keep the parameters.  With `gcn_check_trees` the loss reads one status word back and raises IndexError on a label
+outside [0, num_class)).
 """
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import _lib
 from ..utils import constant
 from .deprel import _DiagLayerFn, _FullAggFn, _zero_pad_row, bilinear_supported, bilinear_traverse, diag_layer  # noqa: F401
 from .embed import _embed, _EmbedFn, embed_inputs  # noqa: F401
+from .head import head_loss, head_predict, linear_act  # noqa: F401
 from .layers import WeightPack, gcn_layer, gcn_layers, gcn_layers_with_acts  # noqa: F401
 from .pooling import pool, pool3, pool3_packed  # noqa: F401
 from .rnn import bilstm
@@ -67,7 +75,34 @@ class GCNClassifier(nn.Module):
 
     def forward(self, inputs, trees=None):
         outputs, pooling_output = self.gcn_model(inputs, trees)
+        if self.opt.get('gcn_native_head', False):
+            return linear_act(outputs, self.classifier.weight, self.classifier.bias, relu=False), pooling_output
         return self.classifier(outputs), pooling_output
+
+    def loss(self, logits, pooling_output, labels):
+        """The training loss of the reference's trainer (model/trainer.py:94-100) from forward()'s two results: CrossEntropyLoss, the
+        conv_l2 decay (opt['conv_l2'] > 0) and the pooling_l2 penalty (opt['pooling_l2'] > 0).  With opt['gcn_native_head'] the cross
+        entropy and the penalty are one launch each way (head_loss)."""
+        l2 = float(self.opt.get('pooling_l2', 0) or 0)
+        if self.opt.get('gcn_native_head', False):
+            check = bool(self.opt.get('gcn_check_trees', True))
+            status = torch.empty((1,), dtype=torch.int32, device=logits.device) if check else None
+            loss = head_loss(logits, labels, pooling_output if l2 > 0 else None, l2, status=status)
+            if check and int(status.item()) & 1:                      # a host sync of its own, only with gcn_check_trees
+                raise IndexError("labels out of range: the classifier has %d classes" % logits.shape[1])
+        else:
+            loss = F.cross_entropy(logits, labels)
+            if l2 > 0:
+                loss = loss + l2 * (pooling_output ** 2).sum(1).mean()
+        if self.opt.get('conv_l2', 0) > 0:
+            loss = loss + self.conv_l2() * self.opt['conv_l2']
+        return loss
+
+    def predict(self, logits):
+        """(class probabilities [B,C], predicted class int64 [B]) as the reference's trainer derives them (model/trainer.py:119-120)."""
+        if self.opt.get('gcn_native_head', False):
+            return head_predict(logits)
+        return F.softmax(logits.detach(), 1), logits.detach().argmax(1)
 
     def get_deprel_emb(self):
         return self.gcn_model.get_deprel_embedding()
@@ -99,6 +134,16 @@ class GCNRelationModel(nn.Module):
         for _ in range(opt['mlp_layers'] - 1):
             mlp += [nn.Linear(opt['hidden_dim'], opt['hidden_dim']), nn.ReLU()]
         self.out_mlp = nn.Sequential(*mlp)
+
+    def _mlp(self, pooled):
+        """out_mlp (gcn.py:66-72, 122); with opt['gcn_native_head'] each Linear + ReLU pair is one linear_act over the module's parameters."""
+        if not self.opt.get('gcn_native_head', False):
+            return self.out_mlp(pooled)
+        x = pooled
+        for lin in self.out_mlp:
+            if isinstance(lin, nn.Linear):
+                x = linear_act(x, lin.weight, lin.bias, relu=True)
+        return x
 
     def get_deprel_embedding(self):
         return self.deprel_emb.weight
@@ -177,11 +222,11 @@ class GCNRelationModel(nn.Module):
             self.gcn._take_request()              # (a forward that raised before it got there leaves nothing behind)
         if isinstance(h, _Pooled):
             pooled = h.value
-            return self.out_mlp(pooled), pooled[:, :self.opt['hidden_dim']]
+            return self._mlp(pooled), pooled[:, :self.opt['hidden_dim']]
         # gcn.py:116-121: three masked poolings and the concat, one pass over h (masks straight from the position tensors)
         pooled = pool3(h, pool_mask, subj_pos, obj_pos, type=self.opt['pooling'])
         h_out = pooled[:, :self.opt['hidden_dim']]
-        return self.out_mlp(pooled), h_out
+        return self._mlp(pooled), h_out
 
 
 class _Pooled(object):

@@ -576,6 +576,34 @@ int gcnpt_embed_bwd(void* stream, const void* g, int g_dtype, const int64_t* wor
                     uint64_t seed_emb, uint64_t seed_in, const uint64_t* seed_dev, int padding_idx, int topn, float* d_emb,
                     float* d_emb_rows, float* d_word_dense, float* d_pos_emb, float* d_ner_emb);
 
+/* ---- the output head, model/gcn.py:31-36, 66-72, 122-125 + model/trainer.py:94-100, 119-120: out_mlp, classifier and the loss.  Everything
+ * float32, exact fp32 MFMA; ONE launch per call; no float atomics, no workspace, no clears (every output element has one owning workgroup
+ * that walks its whole contraction in a fixed order: results are bit-identical run to run).  Any M, K, N, C >= 1.
+ * gcnpt_head_linear_fwd:  y [M,N] = act(x . w^T + b).  x [dev] [M,K] with row stride ldx >= K (elements; a column slice of a wider tensor
+ *   needs no copy), w [dev] [N,K] = nn.Linear.weight as torch stores it (no pack call), b [dev] [N], y [dev] [M,N] contiguous;
+ *   relu = 1: act = ReLU, 0: identity.
+ * gcnpt_head_linear_bwd:  dZ = dy * 1[y > 0] (relu = 1; y is the forward's output) or dy (relu = 0; y unused, may be NULL);
+ *   dx [M,K] = dZ . w (row stride ld_dx >= K; NULL = not wanted), dw [N,K] = dZ^T . x, db [N] = sum over rows of dZ.  The dx tiles and the
+ *   dw / db tiles are workgroups of the same launch.
+ * gcnpt_head_loss_fwd:  logits [dev] [M,C]; labels [dev] int64 [M] or NULL; pooled [dev] [M,H] with row stride ldp >= H, or NULL (no
+ *   penalty term; H, ldp unused).  Every output is optional, at least one must be given:
+ *     loss    float32 [1] = mean_m(-log softmax(logits_m)[labels_m]) + l2 * mean_m sum_{j<H} pooled[m,j]^2   (needs labels; the means are
+ *             summed in a fixed order)
+ *     probs   float32 [M,C] = softmax(logits) (max-subtracted)
+ *     pred    int64 [M] = argmax, the lowest index on ties
+ *     status  int32 [1], written completely: bit 0 = some label lies outside [0, C).  Such a row reads and writes nothing out of bounds and
+ *             contributes nothing to the loss (the mean is still over M rows) -- an error the host may raise, not ignore_index.
+ * gcnpt_head_loss_bwd:  dloss [dev] float32 [1] (never read on the host); the softmax is recomputed from logits (nothing was saved):
+ *     dlogits [M,C] = dloss * (softmax - onehot) / M  (needs labels; a zero row for a label outside [0, C)),  NULL = not wanted
+ *     dpooled [M,H] contiguous = dloss * 2 * l2 / M * pooled[:, :H]  (needs pooled),  NULL = not wanted */
+int gcnpt_head_linear_fwd(void* stream, const float* x, long long ldx, const float* w, const float* b, float* y, int M, int K, int N, int relu);
+int gcnpt_head_linear_bwd(void* stream, const float* dy, const float* y, const float* x, long long ldx, const float* w, float* dx,
+                          long long ld_dx, float* dw, float* db, int M, int K, int N, int relu);
+int gcnpt_head_loss_fwd(void* stream, const float* logits, const int64_t* labels, const float* pooled, long long ldp, int H, float l2, int M,
+                        int C, float* loss, float* probs, int64_t* pred, int32_t* status);
+int gcnpt_head_loss_bwd(void* stream, const float* dloss, const float* logits, const int64_t* labels, const float* pooled, long long ldp, int H,
+                        float l2, int M, int C, float* dlogits, float* dpooled);
+
 #ifdef __cplusplus
 }
 #endif

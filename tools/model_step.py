@@ -8,7 +8,11 @@ weights; eager launches (ctypes + torch), one optimizer-free fwd+bwd per step.  
       (opt['gcn_native_rnn'], model/rnn.py) instead of MIOpen's
   *_native_embed: the same cell with opt['gcn_native_embed'] (lookups, cat, dropouts, cast as one launch; csrc/embed_kernels.hip).
       Every cell has emb_dropout = 0, so neither front end runs its word-type dropout here: input_dropout = 0.5 is what both pay for
+  *_native_head: the same cell with opt['gcn_native_head'] (out_mlp, classifier and the loss on csrc/head_kernels.hip).  Every cell's loss
+      goes through model.loss, so each arm pays for its own loss: torch's cross_entropy + penalty chain, or head_loss
 --cells A,B: only the named cells (C2_gcn, C2_gcn_native_embed, C3_cgcn, ...); --no-copy: skip the copy bandwidth measurement
+--ab A,B [--repeats R]: A/B of two cells in ONE process: both models are built first, then R rounds (default 5) of 100 steps each,
+      alternating A, B, A, B, ...; prints every round's ms per step with the median and the spread (max - min) per arm
 """
 import argparse
 import json
@@ -24,17 +28,19 @@ from gcn_over_pruned_trees_amd.model import gcn, tree  # noqa: E402
 from gcn_over_pruned_trees_amd.utils import synthetic  # noqa: E402
 
 
-def opt_for(rnn, dtype, native_rnn=False, native_embed=False):
+def opt_for(rnn, dtype, native_rnn=False, native_embed=False, native_head=False):
     return dict(vocab_size=5000, emb_dim=300, pos_dim=30, ner_dim=30, hidden_dim=200, num_layers=2, input_dropout=0.5, gcn_dropout=0.5,
                 word_dropout=0.04, emb_dropout=0.0, topn=1e10, prune_k=1, pooling="max", pooling_l2=0.003, mlp_layers=2, no_adj=False,
                 rnn=rnn, rnn_hidden=200, rnn_layers=1, rnn_dropout=0.5, cuda=True, dataset="tacred", num_class=42, adj_type="regular",
-                gcn_dtype=dtype, gcn_check_trees=False, gcn_native_rnn=native_rnn, gcn_native_embed=native_embed)
+                gcn_dtype=dtype, gcn_check_trees=False, gcn_native_rnn=native_rnn, gcn_native_embed=native_embed, gcn_native_head=native_head)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", default="")
     ap.add_argument("--no-copy", action="store_true")
+    ap.add_argument("--ab", default="")
+    ap.add_argument("--repeats", type=int, default=5)
     args = ap.parse_args()
     only = [c for c in args.cells.split(",") if c]
     dev = torch.device("cuda:0")
@@ -48,32 +54,60 @@ def main():
               t(tb["deprel"]), t(tb["head"]), t(tb["subj_pos"]), t(tb["obj_pos"]))
     labels = t(rng.randint(0, 42, size=(B,)).astype(np.int64))
     out = {}
-    for name, rnn, native, embed in (("C2_gcn", False, False, False), ("C2_gcn_native_embed", False, False, True), ("C3_cgcn", True, False, False),
-                                     ("C3_cgcn_native_rnn", True, True, False), ("C3_cgcn_native_rnn_native_embed", True, True, True)):
+    cells = (("C2_gcn", False, False, False, False), ("C2_gcn_native_embed", False, False, True, False), ("C2_gcn_native_head", False, False, False, True),
+             ("C2_gcn_native_embed_native_head", False, False, True, True), ("C3_cgcn", True, False, False, False),
+             ("C3_cgcn_native_rnn", True, True, False, False), ("C3_cgcn_native_rnn_native_embed", True, True, True, False),
+             ("C3_cgcn_native_rnn_native_embed_native_head", True, True, True, True))
+    idx = torch.arange(B, device=dev)
+
+    def make_step(name, dtype):
+        _, rnn, native, embed, head = next(c for c in cells if c[0] == name)
+        torch.manual_seed(1234)
+        model = gcn.GCNClassifier(opt_for(rnn, dtype, native, embed, head)).to(dev).train()
+        cache = tree.TreeCache.build(inputs[5], inputs[6], inputs[7], inputs[4], 1, masks=inputs[1], want_label=False)
+
+        def step(cached):
+            model.zero_grad(set_to_none=True)
+            logits, pooled = model(inputs, trees=cache.batch(idx, T) if cached else None)
+            loss = model.loss(logits, pooled, labels)      # trainer.py:94-100; opt['pooling_l2'] = 0.003, no conv_l2
+            loss.backward()
+            return loss.detach()        # no reference to the autograd graph survives the step (its AccumulateGrad nodes would pin a stream)
+        return step
+
+    def timed(step, cached, n=100):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = step(cached)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n, loss
+
+    if args.ab:
+        a, b = args.ab.split(",")
+        for dtype in ("fp32", "bf16"):
+            steps = {a: make_step(a, dtype), b: make_step(b, dtype)}
+            for cached in (False, True):
+                for s in steps.values():
+                    for _ in range(10):
+                        s(cached)
+                runs = {a: [], b: []}
+                for _ in range(args.repeats):
+                    for name in (a, b):
+                        runs[name].append(round(timed(steps[name], cached)[0] * 1e3, 3))
+                for name in (a, b):
+                    out["%s_%s_%s" % (name, dtype, "cached_trees" if cached else "pruned_in_step")] = dict(
+                        ms_per_step=runs[name], median=float(np.median(runs[name])), spread=round(max(runs[name]) - min(runs[name]), 3))
+        print(json.dumps(out))
+        return
+    for name, _, _, _, _ in cells:
         if only and name not in only:
             continue
         for dtype in ("fp32", "bf16"):
-            torch.manual_seed(1234)
-            model = gcn.GCNClassifier(opt_for(rnn, dtype, native, embed)).to(dev).train()
-            cache = tree.TreeCache.build(inputs[5], inputs[6], inputs[7], inputs[4], 1, masks=inputs[1], want_label=False)
-            idx = torch.arange(B, device=dev)
-
-            def step(cached):
-                model.zero_grad(set_to_none=True)
-                logits, pooled = model(inputs, trees=cache.batch(idx, T) if cached else None)
-                loss = torch.nn.functional.cross_entropy(logits, labels) + 0.003 * (pooled ** 2).sum(1).mean()
-                loss.backward()
-                return loss.detach()        # no reference to the autograd graph survives the step (its AccumulateGrad nodes would pin a stream)
+            step = make_step(name, dtype)
             for cached in (False, True):
                 for _ in range(10):
                     step(cached)
-                torch.cuda.synchronize()
-                n = 100
-                t0 = time.perf_counter()
-                for _ in range(n):
-                    loss = step(cached)
-                torch.cuda.synchronize()
-                dt = (time.perf_counter() - t0) / n
+                dt, loss = timed(step, cached)
                 out["%s_%s_%s" % (name, dtype, "cached_trees" if cached else "pruned_in_step")] = dict(
                     ms_per_step=round(dt * 1e3, 3), sentences_per_s=round(B / dt), loss=float(loss))
     if args.no_copy:
