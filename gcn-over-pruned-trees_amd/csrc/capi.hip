@@ -1,5 +1,5 @@
 // Error state and version of the C-ABI (include/gcnpt.h).  The entry points themselves live next to
-// their kernels in tree_kernels.hip and layer_kernels.hip.
+// their kernels in the other *_kernels.hip files.
 #include <stdarg.h>
 #include <stdlib.h>
 

@@ -45,7 +45,7 @@ constexpr void* g_debug_stamps = nullptr;
 int fail(int code, const char* fmt, ...);
 void note_launch(int grid, int block, size_t lds, size_t kernarg);      // thread-local record for gcnpt_last_launch (capi.hip)
 int option(int key);      // GCNPT_OPT_* of include/gcnpt.h (capi.hip): one relaxed atomic load, no environment access
-// the source-vs-request checks of every rewrite of a batch's tree arrays (tree_kernels.hip); `what` prefixes the messages
+// the source-vs-request checks of every rewrite of a batch's tree arrays (tree_rewrite_kernels.hip); `what` prefixes the messages
 int check_request(const char* what, const int32_t* src_label, const int32_t* src_rowT_ptr, const int32_t* src_colT_idx,
                   const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* label, const int32_t* rowT_ptr,
                   const int32_t* colT_idx, const int32_t* ellT, const uint8_t* pool_mask);

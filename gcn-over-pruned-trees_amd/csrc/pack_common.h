@@ -1,5 +1,6 @@
 // nn.Linear weights -> MFMA fragment order: the device code of gcnpt_pack_weights, shared by the launches that carry it as a side job
-// (the tree build and the tree gather have idle CUs while they run: gcnpt_prune_to_csr_pack, gcnpt_gather_trees_pack).
+// (the tree build and the tree gather have idle CUs while they run: gcnpt_prune_to_csr_pack in tree_kernels.hip, gcnpt_gather_trees_pack
+// in tree_rewrite_kernels.hip).
 #pragma once
 #include "layer_common.h"
 
@@ -78,5 +79,18 @@ __device__ __forceinline__ void pack_side_job(const PackParams& p, int dtype, in
     if (dtype == GCNPT_BF16) pack_fragments<bf16_t>(p, gid0, stride);
     else pack_fragments<float>(p, gid0, stride);
 }
+
+// the weight pack a tree launch may carry as a side job: `blocks` extra workgroups of the launch pack the images described by pk
+struct SideJob {
+    PackParams pk{};
+    int dtype = GCNPT_F32;
+    int blocks = 0;
+};
+
+// sj from the trailing arguments of gcnpt_*_pack / gcnpt_*_packed, for a launch of `threads` per workgroup (enough workgroups for one
+// fragment per thread, at most 192).  optional (the _packed forms): n_layers <= 0 means no side job; otherwise n_layers is checked as
+// gcnpt_pack_weights_multi checks it.  (tree_rewrite_kernels.hip)
+int side_job(SideJob& sj, bool optional, int threads, int n_layers, const float* const* W, const int* H, const int* Din, int dtype,
+             void* const* w_fwd, void* const* w_bwd);
 
 }  // namespace gcnpt

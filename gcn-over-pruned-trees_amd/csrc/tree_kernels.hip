@@ -788,318 +788,9 @@ __global__ void csr_to_adj_kernel(const int32_t* __restrict__ row_ptr, const int
         adj[((size_t)b * T + i) * T + col_idx[e]] = label ? (float)label[e] : 1.0f;
 }
 
-// ---- N4: a batch assembled from a dataset that was pruned once (loader.py:81-141 builds batches from cached features) ----
-// Sentence idx[b] of the cached PrunedTrees (S sentences padded to Ts, capacity cap_s) becomes sentence b of a PrunedTrees
-// for [B, T].  Columns are sentence-local, so entries and ELL heads are copied as they are; only offsets are re-based.
-constexpr int GATHER_THREADS = 256;
-struct TreeArrays {
-    int32_t *row_ptr, *col_idx, *label, *rowT_ptr, *colT_idx, *ell, *ellT;
-    uint8_t* pool_mask;
-    int32_t* status;
-};
-__global__ __launch_bounds__(GATHER_THREADS) void gather_trees_kernel(const TreeArrays src, const int32_t* __restrict__ src_len,
-                                                                     int S, int Ts, int cap_s, const int64_t* __restrict__ idx,
-                                                                     int B, int T, int cap, const TreeArrays dst, const PackParams pk,
-                                                                     int pk_dtype) {
-    __shared__ int s_max[GATHER_THREADS / WAVE];
-    if ((int)blockIdx.x >= B) {    // side job of gcnpt_gather_trees_pack
-        pack_side_job(pk, pk_dtype, B);
-        return;
-    }
-    const int b = blockIdx.x, t = threadIdx.x;
-    const int64_t s64 = idx[b];
-    const bool known = s64 >= 0 && s64 < S;
-    const size_t s = known ? (size_t)s64 : 0;
-    const int len = known ? src_len[s] : 0;
-    const int nnz = src.row_ptr[s * (Ts + 1) + Ts] - (int)s * cap_s;
-    const int nnzT = src.rowT_ptr ? src.rowT_ptr[s * (Ts + 1) + Ts] - (int)s * cap_s : 0;
-    int code = known ? src.status[s] : GCNPT_E_INVALID;
-    if (code == 0 && len > T) code = GCNPT_E_LENGTH;
-    if (code == 0 && (nnz > cap || nnzT > cap)) code = GCNPT_E_CAPACITY;
-    const bool ok = code == 0;                           // otherwise: an empty, fully masked sentence, as the pruner leaves it
-    for (int i = t; i <= T; i += GATHER_THREADS) {
-        const size_t o = s * (Ts + 1) + min(i, Ts);
-        dst.row_ptr[(size_t)b * (T + 1) + i] = b * cap + (ok ? src.row_ptr[o] - (int)s * cap_s : 0);
-        if (dst.rowT_ptr) dst.rowT_ptr[(size_t)b * (T + 1) + i] = b * cap + (ok ? src.rowT_ptr[o] - (int)s * cap_s : 0);
-    }
-    if (ok) {
-        for (int k = t; k < nnz; k += GATHER_THREADS) {
-            dst.col_idx[(size_t)b * cap + k] = src.col_idx[s * cap_s + k];
-            if (dst.label) dst.label[(size_t)b * cap + k] = src.label[s * cap_s + k];
-        }
-        if (dst.colT_idx)
-            for (int k = t; k < nnzT; k += GATHER_THREADS) dst.colT_idx[(size_t)b * cap + k] = src.colT_idx[s * cap_s + k];
-    }
-    typedef int i32x4_t __attribute__((ext_vector_type(4)));       // (a first-class vector: a select between int4 STRUCTS went through scratch memory)
-    const i32x4_t z = {0, 0, 0, 0};
-    for (int q = t; q < 2 * T; q += GATHER_THREADS) {    // ELL heads, 16 bytes at a time
-        const int i = q >> 1;
-        const bool have = ok && i < Ts;
-        const size_t o = (s * Ts + min(i, Ts - 1)) * 2 + (q & 1);
-        reinterpret_cast<i32x4_t*>(dst.ell)[(size_t)b * T * 2 + q] = have ? reinterpret_cast<const i32x4_t*>(src.ell)[o] : z;
-        if (dst.ellT) reinterpret_cast<i32x4_t*>(dst.ellT)[(size_t)b * T * 2 + q] = have ? reinterpret_cast<const i32x4_t*>(src.ellT)[o] : z;
-    }
-    if (dst.pool_mask)
-        for (int i = t; i < T; i += GATHER_THREADS)
-            dst.pool_mask[(size_t)b * T + i] = (ok && i < Ts) ? src.pool_mask[s * Ts + i] : (uint8_t)1;
-    if (t == 0) dst.status[b] = code;
-    if (b == 0) {                                        // status[B] = longest sentence of the batch (gcn.py:97): no memset, no atomics
-        int m = 0;
-        for (int j = t; j < B; j += GATHER_THREADS) {
-            const int64_t sj = idx[j];
-            if (sj >= 0 && sj < S) m = max(m, src_len[sj]);
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d));
-        if ((t & 63) == 0) s_max[t >> 6] = m;
-        __syncthreads();
-        if (t == 0) {
-            for (int w = 1; w < GATHER_THREADS / WAVE; ++w) m = max(m, s_max[w]);
-            dst.status[B] = m;
-        }
-    }
-}
-
-// The same assembly straight into the TOKEN-PACKED layout (what gcnpt_pack_trees makes of gcnpt_gather_trees' arrays, bit for bit): a
-// sentence's offsets are prefix sums over the batch sentences before it, which every workgroup takes from the CACHE itself (lengths and
-// offsets of the cached sentences are all there: no inter-workgroup hand-off as in the pruner's packed form).
-struct GatherPackedDst {
-    int32_t *cu, *row_ptr, *col_idx, *label, *rowT_ptr, *colT_idx, *ell, *ellT;
-    uint8_t *pool_mask, *pool_mask_padded;
-    int32_t *row_sent, *status, *sent_status;
-    int n_rows, nnz_cap;
-};
-__global__ __launch_bounds__(GATHER_THREADS) void gather_trees_packed_kernel(const TreeArrays src, const int32_t* __restrict__ src_len,
-                                                                            int S, int Ts, int cap_s, const int64_t* __restrict__ idx,
-                                                                            int B, int T, const GatherPackedDst dst, const PackParams pk,
-                                                                            int pk_dtype) {
-    __shared__ int s_red[GATHER_THREADS / WAVE][4];
-    if ((int)blockIdx.x >= B) {
-        pack_side_job(pk, pk_dtype, B);
-        return;
-    }
-    const int b = blockIdx.x, t = threadIdx.x;
-    // what sentence j of the batch contributes: its code, rows and entries (a failed sentence: its rows, no entries -- as the padded
-    // assembly leaves it)
-    auto look = [&](int j, int& code, int& len, int& nnz, int& nnzT, size_t& s) {
-        const int64_t s64 = idx[j];
-        const bool known = s64 >= 0 && s64 < S;
-        s = known ? (size_t)s64 : 0;
-        const int l = known ? src_len[s] : 0;
-        nnz = src.row_ptr[s * (Ts + 1) + Ts] - (int)s * cap_s;
-        nnzT = src.rowT_ptr ? src.rowT_ptr[s * (Ts + 1) + Ts] - (int)s * cap_s : 0;
-        code = known ? src.status[s] : GCNPT_E_INVALID;
-        if (code == 0 && l > T) code = GCNPT_E_LENGTH;
-        if (code == 0 && (nnz > 3 * T || nnzT > 3 * T)) code = GCNPT_E_CAPACITY;
-        len = min(l, T);
-        if (code != 0) { nnz = 0; nnzT = 0; }
-    };
-    int a[4] = {0, 0, 0, 0};                                        // rows, entries, transposed entries before b; longest sentence
-    for (int j = t; j < B; j += GATHER_THREADS) {
-        int code, len, nnz, nnzT;
-        size_t s;
-        look(j, code, len, nnz, nnzT, s);
-        if (j < b) { a[0] += len; a[1] += nnz; a[2] += nnzT; }
-        const int64_t sj = idx[j];
-        a[3] = max(a[3], (sj >= 0 && sj < S) ? src_len[sj] : 0);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { a[0] += __shfl_xor(a[0], d); a[1] += __shfl_xor(a[1], d); a[2] += __shfl_xor(a[2], d); a[3] = max(a[3], __shfl_xor(a[3], d)); }
-    if ((t & 63) == 0) { s_red[t >> 6][0] = a[0]; s_red[t >> 6][1] = a[1]; s_red[t >> 6][2] = a[2]; s_red[t >> 6][3] = a[3]; }
-    __syncthreads();
-    int cu = 0, eo = 0, eoT = 0, longest = 0;
-#pragma unroll
-    for (int w = 0; w < GATHER_THREADS / WAVE; ++w) { cu += s_red[w][0]; eo += s_red[w][1]; eoT += s_red[w][2]; longest = max(longest, s_red[w][3]); }
-    int code, len, nnz, nnzT;
-    size_t s;
-    look(b, code, len, nnz, nnzT, s);
-    const bool ok = code == 0;
-    const bool fits = cu + len <= dst.n_rows && eo + nnz <= dst.nnz_cap && eoT + nnzT <= dst.nnz_cap;
-    if (t == 0) {
-        dst.cu[b] = cu;
-        dst.sent_status[b] = code;
-        if (b == 0) dst.sent_status[B] = longest;
-        if (b == B - 1) {
-            dst.cu[B] = cu + len;
-            dst.status[0] = fits ? 0 : GCNPT_E_CAPACITY;
-            dst.status[1] = cu + len;
-            if (fits) {
-                dst.row_ptr[cu + len] = eo + nnz;
-                if (dst.rowT_ptr) dst.rowT_ptr[cu + len] = eoT + nnzT;
-            }
-        }
-    }
-    if (dst.pool_mask_padded)
-        for (int i = t; i < T; i += GATHER_THREADS)
-            dst.pool_mask_padded[(size_t)b * T + i] = (ok && i < Ts) ? src.pool_mask[s * Ts + i] : (uint8_t)1;
-    if (!fits) return;
-    const int rp0 = (int)s * cap_s;
-    for (int i = t; i < len; i += GATHER_THREADS) {
-        dst.row_ptr[cu + i] = eo + (ok ? src.row_ptr[s * (Ts + 1) + i] - rp0 : 0);
-        if (dst.rowT_ptr) dst.rowT_ptr[cu + i] = eoT + (ok ? src.rowT_ptr[s * (Ts + 1) + i] - rp0 : 0);
-        dst.pool_mask[cu + i] = ok ? src.pool_mask[s * Ts + i] : (uint8_t)1;
-        dst.row_sent[cu + i] = b;
-    }
-    for (int k = t; k < nnz; k += GATHER_THREADS) {
-        dst.col_idx[eo + k] = src.col_idx[s * cap_s + k] + cu;
-        if (dst.label) dst.label[eo + k] = src.label[s * cap_s + k];
-    }
-    if (dst.colT_idx)
-        for (int k = t; k < nnzT; k += GATHER_THREADS) dst.colT_idx[eoT + k] = src.colT_idx[s * cap_s + k] + cu;
-    for (int q = t; q < 2 * len; q += GATHER_THREADS) {             // ELL heads, 16 bytes at a time: [count, c0..c2] / [c3..c6], live slots + cu
-        const int i = q >> 1, half = q & 1;
-        const size_t o = (s * Ts + i) * 2 + half;
-        auto shift = [&](const int32_t* e_src, int32_t* e_dst) {
-            const int cnt = ok ? e_src[(s * Ts + i) * 8] : 0;
-            int4 v = ok ? reinterpret_cast<const int4*>(e_src)[o] : make_int4(0, 0, 0, 0);
-            int* e = reinterpret_cast<int*>(&v);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int slot = half * 4 + j - 1;                   // entry number of this word (-1 = the count)
-                if (slot >= 0) e[j] = slot < cnt ? e[j] + cu : 0;
-            }
-            reinterpret_cast<int4*>(e_dst)[((size_t)(cu + i)) * 2 + half] = v;
-        };
-        shift(src.ell, dst.ell);
-        if (dst.ellT) shift(src.ellT, dst.ellT);
-    }
-}
-
-// ---- N1: "pooled-only" rows (gcn.py:116-121 pools h over the tokens of the pruned tree only, and a tree token's row of
-// every layer depends on tree tokens only -- the adjacency has no entry outside the tree).  The kept tokens of a sentence
-// are renumbered 0..kept-1 in token order and the pattern is rewritten in those numbers for a [B, Tc] batch: the layer
-// kernels then run on B*Tc rows instead of B*T (a pruned tree keeps ~1 token in 4-8), with identical values in every
-// kept row.  One workgroup per sentence; slot numbers of the sentence's tokens live in LDS.
-constexpr int COMPACT_THREADS = 256;
-__global__ __launch_bounds__(COMPACT_THREADS) void compact_trees_kernel(const TreeArrays src, int B, int T, int cap, int Tc, int cap_c,
-                                                                       const TreeArrays dst, int64_t* __restrict__ tok,
-                                                                       int32_t* __restrict__ kept_out) {
-    extern __shared__ int c_slot[];                      // [T] slot of token i, or -1
-    __shared__ int s_wave[COMPACT_THREADS / WAVE];
-    __shared__ int s_base;
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) s_base = 0;
-    __syncthreads();
-    // exclusive scan of the in-tree flags, 256 tokens per round
-    for (int i0 = 0; i0 < T; i0 += COMPACT_THREADS) {
-        const int i = i0 + t;
-        const bool in = i < T && src.pool_mask[(size_t)b * T + i] == 0;
-        const unsigned long long m = __ballot(in);
-        if (lane == 0) s_wave[wave] = __popcll(m);
-        __syncthreads();
-        int before = s_base;
-        for (int w = 0; w < wave; ++w) before += s_wave[w];
-        if (i < T) c_slot[i] = in ? before + __popcll(m & ((1ull << lane) - 1ull)) : -1;
-        __syncthreads();
-        if (t == 0) {
-            int tot = s_base;
-            for (int w = 0; w < COMPACT_THREADS / WAVE; ++w) tot += s_wave[w];
-            s_base = tot;
-        }
-        __syncthreads();
-    }
-    const int kept = s_base;
-    const int nnz = src.row_ptr[(size_t)b * (T + 1) + T] - b * cap;
-    const int nnzT = src.rowT_ptr ? src.rowT_ptr[(size_t)b * (T + 1) + T] - b * cap : 0;
-    int code = src.status[b];
-    if (code == 0 && kept > Tc) code = GCNPT_E_LENGTH;
-    if (code == 0 && (nnz > cap_c || nnzT > cap_c)) code = GCNPT_E_CAPACITY;
-    const bool ok = code == 0;
-    if (t == 0) {
-        dst.status[b] = code;
-        kept_out[b] = ok ? kept : 0;
-        if (ok) atomicMax(&dst.status[B], kept);
-    }
-    // slots past the kept tokens (or the whole sentence when it failed): no entries, excluded from pooling
-    const int first_free = ok ? kept : 0;
-    for (int j = first_free + t; j <= Tc; j += COMPACT_THREADS) {
-        dst.row_ptr[(size_t)b * (Tc + 1) + j] = b * cap_c + (ok ? nnz : 0);
-        if (dst.rowT_ptr) dst.rowT_ptr[(size_t)b * (Tc + 1) + j] = b * cap_c + (ok ? nnzT : 0);
-        if (j < Tc) {
-            tok[(size_t)b * Tc + j] = -1;
-            dst.pool_mask[(size_t)b * Tc + j] = 1;
-            int4* e = reinterpret_cast<int4*>(dst.ell + ((size_t)b * Tc + j) * 8);
-            e[0] = make_int4(0, 0, 0, 0); e[1] = make_int4(0, 0, 0, 0);
-            if (dst.ellT) {
-                int4* eT = reinterpret_cast<int4*>(dst.ellT + ((size_t)b * Tc + j) * 8);
-                eT[0] = make_int4(0, 0, 0, 0); eT[1] = make_int4(0, 0, 0, 0);
-            }
-        }
-    }
-    if (!ok) return;
-    auto renumber_head = [&](const int32_t* in, int32_t* out) {       // [count, 7 columns] -> the same in slot numbers
-        const int n = in[0];
-        out[0] = n;
-#pragma unroll
-        for (int k = 1; k < 8; ++k) out[k] = k <= n ? c_slot[min(max(in[k], 0), T - 1)] : 0;
-    };
-    for (int i = t; i < T; i += COMPACT_THREADS) {
-        const int j = c_slot[i];
-        if (j < 0) continue;
-        tok[(size_t)b * Tc + j] = i;
-        dst.pool_mask[(size_t)b * Tc + j] = 0;
-        dst.row_ptr[(size_t)b * (Tc + 1) + j] = b * cap_c + src.row_ptr[(size_t)b * (T + 1) + i] - b * cap;
-        renumber_head(src.ell + ((size_t)b * T + i) * 8, dst.ell + ((size_t)b * Tc + j) * 8);
-        if (dst.rowT_ptr) {
-            dst.rowT_ptr[(size_t)b * (Tc + 1) + j] = b * cap_c + src.rowT_ptr[(size_t)b * (T + 1) + i] - b * cap;
-            renumber_head(src.ellT + ((size_t)b * T + i) * 8, dst.ellT + ((size_t)b * Tc + j) * 8);
-        }
-    }
-    for (int k = t; k < nnz; k += COMPACT_THREADS) {
-        dst.col_idx[(size_t)b * cap_c + k] = c_slot[min(max(src.col_idx[(size_t)b * cap + k], 0), T - 1)];
-        if (dst.label) dst.label[(size_t)b * cap_c + k] = src.label[(size_t)b * cap + k];
-    }
-    if (dst.colT_idx)
-        for (int k = t; k < nnzT; k += COMPACT_THREADS)
-            dst.colT_idx[(size_t)b * cap_c + k] = c_slot[min(max(src.colT_idx[(size_t)b * cap + k], 0), T - 1)];
-}
-
-// what a rewrite of a batch's arrays (gather / pack / compact) may ask of its source: labels, the transposed pattern (all or nothing) and
-// the pool mask only where the source holds them; what: the entry point, for the messages
-int check_request(const char* what, const int32_t* src_label, const int32_t* src_rowT_ptr, const int32_t* src_colT_idx,
-                  const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* label, const int32_t* rowT_ptr,
-                  const int32_t* colT_idx, const int32_t* ellT, const uint8_t* pool_mask) {
-    GCNPT_REQUIRE(!label || src_label, "%s: labels wanted but the source holds none", what);
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr) && (rowT_ptr == nullptr) == (ellT == nullptr),
-                  "%s: rowT_ptr, colT_idx and ellT go together", what);
-    GCNPT_REQUIRE(!rowT_ptr || (src_rowT_ptr && src_colT_idx && src_ellT), "%s: transposed pattern wanted but the source holds none", what);
-    GCNPT_REQUIRE(!pool_mask || src_pool_mask, "%s: pool mask wanted but the source holds none", what);
-    return GCNPT_OK;
-}
-
 }  // namespace gcnpt
 
 using namespace gcnpt;
-
-// the source arrays of a gather / compact launch as the kernel takes them (read only); the transposed pattern only when it is wanted
-static TreeArrays source_arrays(const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label, const int32_t* rowT_ptr,
-                                const int32_t* colT_idx, const int32_t* ell, const int32_t* ellT, const uint8_t* pool_mask,
-                                const int32_t* status, bool want_transpose) {
-    return TreeArrays{const_cast<int32_t*>(row_ptr), const_cast<int32_t*>(col_idx), const_cast<int32_t*>(label),
-                      const_cast<int32_t*>(want_transpose ? rowT_ptr : nullptr), const_cast<int32_t*>(colT_idx), const_cast<int32_t*>(ell),
-                      const_cast<int32_t*>(ellT), const_cast<uint8_t*>(pool_mask), const_cast<int32_t*>(status)};
-}
-
-// the weight pack a tree launch may carry as a side job: `blocks` extra workgroups of the launch pack the images described by pk
-struct SideJob {
-    PackParams pk{};
-    int dtype = GCNPT_F32;
-    int blocks = 0;
-};
-
-// sj from the trailing arguments of gcnpt_*_pack / gcnpt_*_packed, for a launch of `threads` per workgroup (enough workgroups for one
-// fragment per thread, at most 192).  optional (the _packed forms): n_layers <= 0 means no side job; otherwise n_layers is checked as
-// gcnpt_pack_weights_multi checks it
-static int side_job(SideJob& sj, bool optional, int threads, int n_layers, const float* const* W, const int* H, const int* Din, int dtype,
-                    void* const* w_fwd, void* const* w_bwd) {
-    sj = SideJob{};
-    sj.dtype = dtype;
-    if (optional && n_layers <= 0) return GCNPT_OK;
-    const int rc = fill_pack_params(sj.pk, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
-    if (rc != GCNPT_OK) return rc;
-    sj.blocks = (int)std::min<long long>(192, (sj.pk.first[n_layers] + threads - 1) / threads);
-    return GCNPT_OK;
-}
 
 static int prune_impl(void* stream, const int64_t* head, const int64_t* subj_pos, const int64_t* obj_pos,
                       const int64_t* deprel, const uint8_t* pad_mask, const int32_t* len, int B, int T,
@@ -1202,107 +893,6 @@ extern "C" int gcnpt_csr_to_adj(void* stream, const int32_t* row_ptr, const int3
     GCNPT_HIP_CHECK(hipMemsetAsync(adj, 0, sizeof(float) * (size_t)B * T * T, s));
     const int rows = B * T;
     hipLaunchKernelGGL(csr_to_adj_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, s, row_ptr, col_idx, label, B, T, adj);
-    GCNPT_HIP_CHECK(hipGetLastError());
-    return GCNPT_OK;
-}
-
-static int gather_impl(void* stream, const int32_t* src_row_ptr, const int32_t* src_col_idx, const int32_t* src_label,
-                       const int32_t* src_rowT_ptr, const int32_t* src_colT_idx, const int32_t* src_ell,
-                       const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* src_status,
-                       const int32_t* src_len, int S, int Ts, int cap_s, const int64_t* idx, int B, int T, int cap,
-                       int32_t* row_ptr, int32_t* col_idx, int32_t* label, int32_t* rowT_ptr, int32_t* colT_idx,
-                       int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status, const SideJob& sj) {
-    GCNPT_REQUIRE(src_row_ptr && src_col_idx && src_ell && src_status && src_len && idx, "gather_trees: null cache pointer");
-    GCNPT_REQUIRE(row_ptr && col_idx && ell && status, "gather_trees: null output pointer");
-    GCNPT_REQUIRE(S > 0 && Ts > 0 && cap_s > 0 && B > 0 && T > 0 && cap > 0, "gather_trees: sizes must be positive");
-    const int rc = check_request("gather_trees", src_label, src_rowT_ptr, src_colT_idx, src_ellT, src_pool_mask, label, rowT_ptr, colT_idx, ellT,
-                                 pool_mask);
-    if (rc != GCNPT_OK) return rc;
-    if ((long long)B * cap > 0x7fffffffLL) return fail(GCNPT_E_UNSUPPORTED, "gather_trees: B*cap overflows int32");
-    const TreeArrays src = source_arrays(src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask,
-                                         src_status, rowT_ptr != nullptr);
-    const TreeArrays dst{row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status};
-    hipLaunchKernelGGL(gather_trees_kernel, dim3(B + sj.blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, src, src_len, S, Ts, cap_s, idx,
-                       B, T, cap, dst, sj.pk, sj.dtype);
-    GCNPT_HIP_CHECK(hipGetLastError());
-    return GCNPT_OK;
-}
-
-extern "C" int gcnpt_gather_trees(void* stream, const int32_t* src_row_ptr, const int32_t* src_col_idx, const int32_t* src_label,
-                                  const int32_t* src_rowT_ptr, const int32_t* src_colT_idx, const int32_t* src_ell,
-                                  const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* src_status,
-                                  const int32_t* src_len, int S, int Ts, int cap_s, const int64_t* idx, int B, int T, int cap,
-                                  int32_t* row_ptr, int32_t* col_idx, int32_t* label, int32_t* rowT_ptr, int32_t* colT_idx,
-                                  int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status) {
-    return gather_impl(stream, src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask, src_status,
-                       src_len, S, Ts, cap_s, idx, B, T, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status,
-                       SideJob{});
-}
-
-extern "C" int gcnpt_gather_trees_pack(void* stream, const int32_t* src_row_ptr, const int32_t* src_col_idx, const int32_t* src_label,
-                                       const int32_t* src_rowT_ptr, const int32_t* src_colT_idx, const int32_t* src_ell,
-                                       const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* src_status,
-                                       const int32_t* src_len, int S, int Ts, int cap_s, const int64_t* idx, int B, int T, int cap,
-                                       int32_t* row_ptr, int32_t* col_idx, int32_t* label, int32_t* rowT_ptr, int32_t* colT_idx,
-                                       int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status, int n_layers,
-                                       const float* const* W, const int* H, const int* Din, int dtype, void* const* w_fwd,
-                                       void* const* w_bwd) {
-    SideJob sj;
-    const int rc = side_job(sj, false, GATHER_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
-    if (rc != GCNPT_OK) return rc;
-    return gather_impl(stream, src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask, src_status,
-                       src_len, S, Ts, cap_s, idx, B, T, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status, sj);
-}
-
-extern "C" int gcnpt_gather_trees_packed(void* stream, const int32_t* src_row_ptr, const int32_t* src_col_idx, const int32_t* src_label,
-                                        const int32_t* src_rowT_ptr, const int32_t* src_colT_idx, const int32_t* src_ell,
-                                        const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* src_status,
-                                        const int32_t* src_len, int S, int Ts, int cap_s, const int64_t* idx, int B, int T,
-                                        int32_t* cu_seqlens, int32_t* row_ptr, int32_t* col_idx, int32_t* label, int32_t* rowT_ptr,
-                                        int32_t* colT_idx, int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* row_sent, int n_rows,
-                                        int nnz_cap, int32_t* status, int32_t* sent_status, uint8_t* pool_mask_padded, int n_layers,
-                                        const float* const* W, const int* H, const int* Din, int dtype, void* const* w_fwd,
-                                        void* const* w_bwd) {
-    GCNPT_REQUIRE(src_row_ptr && src_col_idx && src_ell && src_status && src_len && src_pool_mask && idx, "gather_trees_packed: null cache pointer");
-    GCNPT_REQUIRE(cu_seqlens && row_ptr && col_idx && ell && pool_mask && row_sent && status && sent_status, "gather_trees_packed: null output pointer");
-    GCNPT_REQUIRE(S > 0 && Ts > 0 && cap_s > 0 && B > 0 && T > 0 && n_rows > 0 && nnz_cap > 0, "gather_trees_packed: sizes must be positive");
-    int rc = check_request("gather_trees_packed", src_label, src_rowT_ptr, src_colT_idx, src_ellT, src_pool_mask, label, rowT_ptr, colT_idx, ellT,
-                           pool_mask);
-    if (rc != GCNPT_OK) return rc;
-    SideJob sj;
-    rc = side_job(sj, true, GATHER_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
-    if (rc != GCNPT_OK) return rc;
-    const TreeArrays src = source_arrays(src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask,
-                                         src_status, rowT_ptr != nullptr);
-    const GatherPackedDst dst{cu_seqlens, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, pool_mask_padded, row_sent, status,
-                              sent_status, n_rows, nnz_cap};
-    hipLaunchKernelGGL(gather_trees_packed_kernel, dim3(B + sj.blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, src, src_len, S, Ts, cap_s, idx,
-                       B, T, dst, sj.pk, sj.dtype);
-    GCNPT_HIP_CHECK(hipGetLastError());
-    return GCNPT_OK;
-}
-
-extern "C" int gcnpt_compact_trees(void* stream, const int32_t* src_row_ptr, const int32_t* src_col_idx, const int32_t* src_label,
-                                   const int32_t* src_rowT_ptr, const int32_t* src_colT_idx, const int32_t* src_ell,
-                                   const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* src_status, int B, int T,
-                                   int cap, int Tc, int cap_c, int32_t* row_ptr, int32_t* col_idx, int32_t* label,
-                                   int32_t* rowT_ptr, int32_t* colT_idx, int32_t* ell, int32_t* ellT, uint8_t* pool_mask,
-                                   int32_t* status, int64_t* tok, int32_t* kept) {
-    GCNPT_REQUIRE(src_row_ptr && src_col_idx && src_ell && src_pool_mask && src_status, "compact_trees: null source pointer");
-    GCNPT_REQUIRE(row_ptr && col_idx && ell && pool_mask && status && tok && kept, "compact_trees: null output pointer");
-    GCNPT_REQUIRE(B > 0 && T > 0 && cap > 0 && Tc > 0 && cap_c > 0, "compact_trees: sizes must be positive");
-    const int rc = check_request("compact_trees", src_label, src_rowT_ptr, src_colT_idx, src_ellT, src_pool_mask, label, rowT_ptr, colT_idx, ellT,
-                                 pool_mask);
-    if (rc != GCNPT_OK) return rc;
-    if ((long long)B * cap_c > 0x7fffffffLL) return fail(GCNPT_E_UNSUPPORTED, "compact_trees: B*cap_c overflows int32");
-    const size_t lds = sizeof(int) * (size_t)T;
-    if (lds > 60 * 1024) return fail(GCNPT_E_UNSUPPORTED, "compact_trees: T=%d exceeds the %d tokens a sentence may have", T, 60 * 1024 / 4);
-    const TreeArrays src = source_arrays(src_row_ptr, src_col_idx, src_label, src_rowT_ptr, src_colT_idx, src_ell, src_ellT, src_pool_mask,
-                                         src_status, rowT_ptr != nullptr);
-    const TreeArrays dst{row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status};
-    hipStream_t s = (hipStream_t)stream;
-    GCNPT_HIP_CHECK(hipMemsetAsync(status + B, 0, sizeof(int32_t), s));         // status[B] = most kept tokens in a sentence (atomicMax)
-    hipLaunchKernelGGL(compact_trees_kernel, dim3(B), dim3(COMPACT_THREADS), lds, s, src, B, T, cap, Tc, cap_c, dst, tok, kept);
     GCNPT_HIP_CHECK(hipGetLastError());
     return GCNPT_OK;
 }

@@ -6,7 +6,8 @@ turns it into a dense float32 [T,T] matrix (model/tree.py:167 tree_to_adj), afte
 back from the GPU (model/gcn.py:96-110).  Here the whole batch is pruned by one HIP kernel launch
 (csrc/tree_kernels.hip) straight from the loader tensors that already sit in HBM, and what comes out
 is the CSR pattern of that matrix (`PrunedTrees`).  `PrunedTrees.to_dense()` gives the reference's
-labelled adjacency back for callers that want it.
+labelled adjacency back for callers that want it.  The rewrites of those arrays into another layout
+(pack, compact, the TreeCache's gathers) are the kernels of csrc/tree_rewrite_kernels.hip.
 
 No CPU path exists: these functions raise if the tensors are not on a GPU or libgcnpt.so is missing.
 """
@@ -502,12 +503,7 @@ class TreeCache(object):
         (sum of min(len, T)) when the caller knows it -- the loader does; otherwise it is summed on the device (one sync)."""
         idx = _lib.require_gpu(idx).to(torch.int64).contiguous()
         src, B, T = self.trees, int(idx.numel()), int(T)
-        want_label = (src.label is not None) if want_label is None else want_label
-        if want_label and src.label is None:
-            raise ValueError("the cache was built without labels")
-        tr = bool(want_transpose)
-        if tr and src.rowT_ptr is None:
-            raise ValueError("the cache was built without the transposed pattern")
+        want_label, tr = self._request(src, want_label, want_transpose)
         if n_rows is None:
             ok = (idx >= 0) & (idx < len(self))
             n_rows = int((self.lens.index_select(0, idx.clamp(0, len(self) - 1)).clamp(max=T) * ok).sum().item())
@@ -520,11 +516,20 @@ class TreeCache(object):
         return out
 
     @staticmethod
-    def _gather(src, lens, idx, T, want_label, pack=None):
-        B = int(idx.numel())
-        want_label = (src.label is not None) if want_label is None else want_label
+    def _request(src, want_label, want_transpose):
+        """(want_label, want_transpose) of a batch from the cached `src` (want_label None: whatever the cache holds); raises for what the
+        cache was built without."""
+        want_label = (src.label is not None) if want_label is None else bool(want_label)
         if want_label and src.label is None:
             raise ValueError("the cache was built without labels")
+        if want_transpose and src.rowT_ptr is None:
+            raise ValueError("the cache was built without the transposed pattern")
+        return want_label, bool(want_transpose)
+
+    @classmethod
+    def _gather(cls, src, lens, idx, T, want_label, pack=None):
+        B = int(idx.numel())
+        want_label, _ = cls._request(src, want_label, True)
         cap = 3 * T
         out = _alloc(B, T, cap, src.device, want_label, True)
         args = (_lib.stream(), *src.c_args(), _lib.ptr(lens), src.B, src.T, src.cap, _lib.ptr(idx), B, T, cap, *out.c_args())

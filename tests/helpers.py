@@ -1,5 +1,6 @@
 """Shared by the CPU and GPU test modules: rebuild fixture inputs, tolerances, device helpers, the row tile's LDS count."""
 import contextlib
+import functools
 
 import numpy as np
 
@@ -44,6 +45,35 @@ def layer_case(name):
     g.update(x=x, gy=gy, Ws=Ws, bs=bs, adj=dense_from_coo(g["coo"], B, T),
              masks=np.arange(T)[None, :] >= g["lens"][:, None])
     return g
+
+
+@functools.lru_cache(maxsize=None)
+def star_parse_case():
+    """Star-shaped parses, for the paths that ordinary trees (rows of <= 4 entries) never reach: B = 6, T = 120, K = 3, one head with
+    13 ... 38 kept children per sentence, more than 64 rows with edges in some sentence.  Returns (batch, the C oracle's result, K);
+    shared between tests, so read only."""
+    from oracle import prune_ref
+    B, T, K = 6, 120, 3
+    rng = np.random.RandomState(77)
+    g = synthetic.random_tree_batch(78, B, T, np.array([120, 118, 115, 110, 104, 100], np.int32))
+    for b in range(B):
+        n = int(g["lens"][b])
+        hub = int(g["subj_span"][b, 0])                                   # a subject token: on the path, so its children survive K >= 1
+        kids = rng.permutation(np.setdiff1d(np.arange(n), [hub]))[: 13 + 5 * b]
+        # re-hang `kids` under the hub unless that would detach the hub from the root (skip the hub's own ancestors)
+        anc, a = set(), hub
+        while g["head"][b, a] != 0:
+            a = int(g["head"][b, a]) - 1
+            anc.add(a)
+        for c in kids:
+            if int(c) not in anc:
+                g["head"][b, c] = hub + 1
+    want = prune_ref.batch_adj(g["head"], g["subj_pos"], g["obj_pos"], g["deprel"], g["lens"], K)
+    assert want["rc"] == 0
+    A = want["adj"] != 0
+    assert (A.sum(2).max(1) >= 13).all(), "the fixture must have a row with more than 12 entries in every sentence"
+    assert (A.any(2).sum(1) > 64).any(), "and more than 64 rows with edges in some sentence"
+    return g, want, K
 
 
 LAYER_CASES = ["layers_c1_l1.npz", "layers_c1_l2.npz", "layers_c2s.npz", "layers_c3s.npz", "layers_c5s.npz"]

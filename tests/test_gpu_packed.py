@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from conftest import dense_from_coo, load_golden
-from helpers import FWD_RTOL, GRAD_RTOL, max_rel
+from helpers import FWD_RTOL, GRAD_RTOL, max_rel, star_parse_case
 from gcn_over_pruned_trees_amd.utils import synthetic
 
 pytestmark = pytest.mark.gpu
@@ -221,6 +221,49 @@ def test_cache_batch_packed_equals_pack_of_batch(api, dev, shape):
         small = cache.batch_packed(whole, Ts, n_rows=ok_rows - 2)
         torch.cuda.synchronize()
         assert int(small.status[0]) == -8                               # GCNPT_E_CAPACITY: reported, not overrun
+
+
+@pytest.mark.parametrize("want_T", [True, False], ids=["with_transpose", "forward_only"])
+def test_packed_producers_on_star_parses(api, dev, want_T):
+    """Ordinary trees have rows of <= 4 entries, so they never show the packed ELL-head shift all 7 slots live with a count above 7
+    (the row continues in the CSR).  Star-shaped parses (hubs with 13 ... 38 children) do: the three producers of the packed layout
+    -- gcnpt_pack_trees of the pruner's arrays, the pruner itself, the cache's gather -- agree array by array, and every row's ELL head
+    and CSR segment are those of the C oracle's dense adjacency, shifted by cu[b]."""
+    gcn, tree = api
+    g, want, K = star_parse_case()
+    B, T = g["head"].shape
+    lens = g["lens"].astype(np.int64)
+    args = [_t(g[k], dev) for k in ("head", "subj_pos", "obj_pos", "deprel")]
+    lens_dev = _t(lens.astype(np.int32), dev)
+    padded = tree.prune_to_csr(*args, K, lens=lens_dev, want_label=True, want_transpose=want_T).check(expect_maxlen=T)
+    two = padded.pack(lens.tolist()).check()
+    one = tree.prune_to_csr_packed(*args, K, lens.tolist(), want_label=True, want_transpose=want_T)
+    cache = tree.TreeCache.build(*args, K, lens=lens_dev, want_label=True)
+    gathered = cache.batch_packed(torch.arange(B, device=dev), T, want_label=True, want_transpose=want_T)
+    for other, what in ((one, "prune_to_csr_packed"), (gathered, "batch_packed")):
+        _same_packed(other, two, what)
+        assert torch.equal(other.padded.status, padded.status), what
+        assert torch.equal(other.padded.pool_mask, padded.pool_mask), what
+    A = want["adj"] != 0
+    cu = np.concatenate([[0], np.cumsum(lens)])
+    np.testing.assert_array_equal(two.cu_seqlens.cpu().numpy(), cu)
+    sides = [(two.ell, two.row_ptr, two.col_idx, A)]
+    if want_T:
+        sides.append((two.ellT, two.rowT_ptr, two.colT_idx, A.transpose(0, 2, 1)))
+    for ell, row_ptr, col_idx, M in sides:
+        e, rp, ci = ell.view(-1, 8).cpu().numpy(), row_ptr.cpu().numpy(), col_idx.cpu().numpy()
+        longest = 0
+        for b in range(B):
+            for i in range(int(lens[b])):
+                r = cu[b] + i
+                cols = np.flatnonzero(M[b, i])
+                head = np.zeros(8, np.int64)
+                head[0] = len(cols)
+                head[1:1 + min(len(cols), 7)] = cols[:7] + cu[b]
+                np.testing.assert_array_equal(e[r], head)
+                np.testing.assert_array_equal(ci[rp[r]:rp[r + 1]] - cu[b], cols)
+                longest = max(longest, len(cols))
+        assert longest > 7
 
 
 @pytest.mark.parametrize("width,dtype", [(360, torch.float32), (300, torch.bfloat16), (200, torch.bfloat16), (7, torch.float32)])

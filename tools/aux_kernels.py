@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Runs the auxiliary kernels (pool3, diagonal_deprel layer, tree gather) at the bench shape a few hundred times, for
+"""Runs the auxiliary kernels (pool3, diagonal_deprel layer, the four tree-array rewrites) at the bench shape a few hundred times, for
 `rocprofv3 --kernel-trace --stats` (developer tool: their durations are not part of the headline step)."""
 import os
 import sys
@@ -31,8 +31,15 @@ def main():
         for _ in range(100):
             y = gcn.diag_layer(h, E, deprel, trees, 0.5, 3)
             y.backward(torch.ones_like(y))
+    # the four rewrites of the tree arrays; host lengths and a fixed Tc, so nothing synchronises
+    lens = tb["lens"].tolist()
+    n_rows = int(sum(lens))
+    Tc = int((~trees.pool_mask.view(B, T)).sum(1).max())
     for _ in range(100):
         cache.batch(idx, T)
+        trees.pack(lens)
+        cache.batch_packed(idx, T, n_rows=n_rows)
+        trees.compact(Tc=Tc)
     torch.cuda.synchronize()
     print("done")
 
