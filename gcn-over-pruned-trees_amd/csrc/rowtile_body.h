@@ -33,7 +33,9 @@ __device__ __forceinline__ void rowtile_body(const RowTileParams& p, const int b
     constexpr bool MASKED = BWD && !DZIN;                       // the loader computes dZ = dY * 1[Y>0] * scale / (deg+1) itself
     constexpr int KSTEP = sizeof(CT) == 2 ? 32 : 16;            // K consumed per fragment
     constexpr bool WIDE = MASKED && sizeof(IT) == 4;            // two fp32 streams per row: fewer rows in flight per thread
-    constexpr int ITEMS = WIDE ? 2 : 3;                         // 8-element chunks a thread gathers per batch
+    // the K-fitted shape (rowtile_shape gives it only layers of <= 7 k-steps, Kpad <= 224): 2 chunks per thread cover the tile
+    constexpr bool KFIT = NWV == 8 && NTW == 2 && KSMAX == 7;
+    constexpr int ITEMS = (WIDE || KFIT) ? 2 : 3;               // 8-element chunks a thread gathers per batch
     constexpr int NBU = WIDE ? 2 : 4;                           // neighbour rows fetched together
     const int stride = lds_stride_dw(p.Kpad * (int)sizeof(CT) / 4) * 4 / (int)sizeof(CT);     // S row stride, CT elements
     const int ncols_pass = RTW * NTW * 16;
@@ -360,7 +362,8 @@ static inline bool use_four_waves(const RowTileParams& p) {
 
 // The configuration of the one-shot form launch_rowtile takes for a layer: waves per workgroup, output tiles per wave (the smallest of
 // {2,3,4} that covers NOUT in one pass of 8 waves; 4-wave workgroups for big batches) and k-steps of weight fragments resident in
-// registers (as many as ~128 VGPRs allow).  Rows that cannot be read 16 bytes at a time (width not a multiple of 8, unaligned base) take
+// registers (as many as ~128 VGPRs allow; with 2 tiles per wave no more than the layer has, when that is <= 7).  Rows that cannot be
+// read 16 bytes at a time (width not a multiple of 8, unaligned base) take
 // the element-load instantiation.  ONE function for the launch and for the wide form's dispatch (rowtile_fwd_too_wide).
 struct RtShape { int nwv, ntw, ksmax; };
 static inline RtShape rowtile_shape(const RowTileParams& p, int ct_size, bool bwd) {
@@ -374,8 +377,11 @@ static inline RtShape rowtile_shape(const RowTileParams& p, int ct_size, bool bw
         return RtShape{4, 5, 4};                                          // 300 / 600 columns: one / two passes of 20 tiles
     }
     if (n_tiles <= RT_WAVES * 2) {
-        // 13 k-steps = the C-GCN input width (2 x 200 BiLSTM states): one more resident k-step instead of a second load phase
-        if (p.Kpad / (ct_size == 2 ? 32 : 16) == 13) return RtShape{8, 2, 13};
+        // 13 k-steps = the C-GCN input width (2 x 200 BiLSTM states): one more resident k-step instead of a second load phase;
+        // <= 7 k-steps (the 200-wide hidden layers): only those are requested and held, the tile's own rows take 2 chunks per thread
+        const int ksteps = p.Kpad / (ct_size == 2 ? 32 : 16);
+        if (ksteps == 13) return RtShape{8, 2, 13};
+        if (ksteps <= 7) return RtShape{8, 2, 7};
         return RtShape{8, 2, 12};
     }
     if (n_tiles <= RT_WAVES * 3) return RtShape{8, 3, 7};
@@ -469,6 +475,7 @@ static inline int launch_rowtile_vec(hipStream_t s, const RowTileParams& p) {
     }
     if (sh.ntw == 2) {
         if (sh.ksmax == 13) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 13, DZIN>(s, p);
+        if (sh.ksmax == 7) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 7, DZIN>(s, p);
         return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 2, 12, DZIN>(s, p);
     }
     if (sh.ntw == 3) return launch_rowtile_cfg<CT, IT, OT, BWD, VEC, 3, 7, DZIN>(s, p);
