@@ -44,6 +44,24 @@ class _FullAggFn(torch.autograd.Function):
         return dyf, dyr, (dagg if has_self else None), None, None, None, None, None, None, None, None
 
 
+def operand_format(compute):
+    """(k-step width, torch dtype) of the traversal kernels' operands in precision `compute` (csrc/bilinear_kernels.hip: KSTEP, op_t)."""
+    return (32, torch.bfloat16) if compute == _lib.BF16 else (16, torch.float32)
+
+
+def padded_cols(src, k, dtype):
+    """Zero-padded [M, ceil(W/k)*k] copy of src [M, W] in `dtype`."""
+    M, W = src.shape
+    out = torch.zeros((M, (W + k - 1) // k * k), dtype=dtype, device=src.device)
+    out[:, :W] = src
+    return out
+
+
+def image_buffer(n_bytes, dev):
+    """Uninitialised buffer for a fragment image of n_bytes bytes."""
+    return torch.empty((n_bytes,), dtype=torch.uint8, device=dev)
+
+
 class _BilinearFn(torch.autograd.Function):
     """y = sum_d e[:,d] * (x @ W3[d]) + e @ b3 (reference traverse_deprel, model/gcn.py:400-415) with the contraction on
     csrc/bilinear_kernels.hip in either precision: exact fp32 MFMA (the module's default) or bf16 operands with fp32 accumulation.
@@ -57,13 +75,11 @@ class _BilinearFn(torch.autograd.Function):
         D = e.shape[1]
         H = weight.shape[0] // D
         lib, st, dev = _lib.lib(), _lib.stream(), xt.device
-        k = 32 if compute == _lib.BF16 else 16
-        op_dtype = torch.bfloat16 if compute == _lib.BF16 else torch.float32
+        k, op_dtype = operand_format(compute)
         w32 = weight.detach().to(torch.float32).contiguous()
-        img = torch.empty((lib.gcnpt_bilinear_packed_bytes(D, Tin, H, compute),), dtype=torch.uint8, device=dev)
+        img = image_buffer(lib.gcnpt_bilinear_packed_bytes(D, Tin, H, compute), dev)
         _lib.check(lib.gcnpt_bilinear_pack(st, _lib.ptr(w32), D, Tin, H, _lib.ptr(img), 0, compute))
-        xb = torch.zeros((M, (Tin + k - 1) // k * k), dtype=op_dtype, device=dev)
-        xb[:, :Tin] = xt.detach()
+        xb = padded_cols(xt.detach(), k, op_dtype)
         e32 = e.detach().to(torch.float32).contiguous()
         planes = torch.empty((lib.gcnpt_bilinear_planes(M, D, Tin, H, compute), M, H), dtype=torch.float32, device=dev)
         _lib.check(lib.gcnpt_bilinear_fwd(st, _lib.ptr(xb), _lib.ptr(e32), _lib.ptr(img), M, D, Tin, H, _lib.ptr(planes), compute))
@@ -80,8 +96,7 @@ class _BilinearFn(torch.autograd.Function):
         D = e.shape[1]
         H = weight.shape[0] // D
         lib, st, dev = _lib.lib(), _lib.stream(), xt.device
-        k = 32 if compute == _lib.BF16 else 16
-        op_dtype = torch.bfloat16 if compute == _lib.BF16 else torch.float32
+        k, op_dtype = operand_format(compute)
         gy = gy.to(torch.float32).contiguous()
         x32, e32 = xt.to(torch.float32), e.to(torch.float32).contiguous()
         w32 = weight.detach().to(torch.float32).contiguous()
@@ -90,10 +105,9 @@ class _BilinearFn(torch.autograd.Function):
         on_kernel = bool(lib.gcnpt_bilinear_supported(D, H, Tin, compute))         # the transposed problem contracts over H
         if ctx.needs_input_grad[0]:
             if on_kernel:       # dx = sum_d e_d (gy @ W3[d]^T): the forward kernel on the transposed weight image
-                imgT = torch.empty((lib.gcnpt_bilinear_packed_bytes(D, H, Tin, compute),), dtype=torch.uint8, device=dev)
+                imgT = image_buffer(lib.gcnpt_bilinear_packed_bytes(D, H, Tin, compute), dev)
                 _lib.check(lib.gcnpt_bilinear_pack(st, _lib.ptr(w32), D, Tin, H, _lib.ptr(imgT), 1, compute))
-                gyb = torch.zeros((M, (H + k - 1) // k * k), dtype=op_dtype, device=dev)
-                gyb[:, :H] = gy
+                gyb = padded_cols(gy, k, op_dtype)
                 planes = torch.empty((lib.gcnpt_bilinear_planes(M, D, H, Tin, compute), M, Tin), dtype=torch.float32, device=dev)
                 _lib.check(lib.gcnpt_bilinear_fwd(st, _lib.ptr(gyb), _lib.ptr(e32), _lib.ptr(imgT), M, D, H, Tin, _lib.ptr(planes), compute))
                 dx = planes.sum(0)
@@ -105,14 +119,12 @@ class _BilinearFn(torch.autograd.Function):
             _lib.check(lib.gcnpt_bilinear_bwd_e(st, _lib.ptr(xb), _lib.ptr(gy), _lib.ptr(img), M, D, Tin, H, _lib.ptr(planes), compute))
             de = torch.addmm(planes.sum(0), gy, b3.t())
         if ctx.needs_input_grad[2]:                                       # dW3[d] = (e_d * x)^T gy without the [M, D*Tin] outer product
-            u8 = dict(dtype=torch.uint8, device=dev)
-            xI = torch.empty((lib.gcnpt_rows_image_bytes(M, Tin, compute),), **u8)
-            gI = torch.empty((lib.gcnpt_rows_image_bytes(M, H, compute),), **u8)
+            xI = image_buffer(lib.gcnpt_rows_image_bytes(M, Tin, compute), dev)
+            gI = image_buffer(lib.gcnpt_rows_image_bytes(M, H, compute), dev)
             x32c = x32.contiguous()
             _lib.check(lib.gcnpt_rows_pack(st, _lib.ptr(x32c), M, Tin, _lib.ptr(xI), compute))
             _lib.check(lib.gcnpt_rows_pack(st, _lib.ptr(gy), M, H, _lib.ptr(gI), compute))
-            eT = torch.zeros((D, (M + k - 1) // k * k), dtype=torch.float32, device=dev)
-            eT[:, :M] = e32.t()
+            eT = padded_cols(e32.t(), k, torch.float32)
             dW32 = torch.empty(weight.shape, dtype=torch.float32, device=dev)
             _lib.check(lib.gcnpt_bilinear_bwd_w(st, _lib.ptr(xI), _lib.ptr(gI), _lib.ptr(eT), M, D, Tin, H, _lib.ptr(dW32), compute))
             dW = dW32.to(weight.dtype)

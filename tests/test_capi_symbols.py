@@ -83,6 +83,34 @@ def test_argument_validation_needs_no_gpu():
     assert b"labels wanted" in L.gcnpt_last_error()
 
 
+def test_bilinear_host_arithmetic_needs_no_gpu():
+    """The sizes and plane counts the Python side allocates the full_deprel traversal's buffers with (csrc/bilinear_kernels.hip:
+    one plan for both precisions).  Pairs are (bf16, fp32)."""
+    from gcn_over_pruned_trees_amd import _lib
+    L = _lib.lib()
+    both = lambda fn, *a: tuple(fn(*a, c) for c in (_lib.BF16, _lib.F32))  # noqa: E731
+    for (M, D, Tin, H), packed, rows in (((1000, 50, 200, 200), (4659200, 8652800), (425984, 838656)),
+                                         ((20, 2, 264, 264), (313344, 591872), (17408, 34816))):
+        assert both(L.gcnpt_bilinear_packed_bytes, D, Tin, H) == packed, (M, D, Tin, H)
+        assert both(L.gcnpt_rows_image_bytes, M, Tin) == rows, (M, D, Tin, H)
+    for (M, D, Tin, H), planes, de_planes, planes_t in (((1000, 50, 200, 200), (10, 6), (5, 5), (10, 6)),
+                                                        ((300, 200, 96, 200), (25, 17), (5, 5), (50, 40)),
+                                                        ((520, 24, 300, 300), (12, 6), (14, 14), (12, 6)),
+                                                        ((70, 5, 600, 296), (3, 3), (21, 21), (2, 2)),
+                                                        ((20, 2, 264, 264), (2, 2), (12, 12), (2, 2))):
+        assert both(L.gcnpt_bilinear_planes, M, D, Tin, H) == planes, (M, D, Tin, H)
+        assert both(L.gcnpt_bilinear_de_planes, M, D, Tin, H) == de_planes, (M, D, Tin, H)
+        assert both(L.gcnpt_bilinear_planes, M, D, H, Tin) == planes_t, (M, D, Tin, H)          # the transposed problem (dx)
+    for H in (1, 16, 200):
+        assert both(L.gcnpt_bilinear_supported, 2, 2048, H) == (1, 1) and both(L.gcnpt_bilinear_supported, 2, 2049, H) == (0, 0)
+    for M in (0, -3):
+        assert both(L.gcnpt_bilinear_planes, M, 2, 264, 264) == (0, 0) and both(L.gcnpt_bilinear_de_planes, M, 2, 264, 264) == (0, 0)
+    for bad in (-1, 2, 7):
+        assert L.gcnpt_bilinear_planes(20, 2, 264, 264, bad) == 0 and L.gcnpt_bilinear_de_planes(20, 2, 264, 264, bad) == 0
+        assert L.gcnpt_bilinear_packed_bytes(2, 264, 264, bad) == 0 and L.gcnpt_rows_image_bytes(20, 264, bad) == 0
+        assert L.gcnpt_bilinear_supported(2, 264, 264, bad) == 0
+
+
 def test_no_cpu_fallback():
     import torch
     from gcn_over_pruned_trees_amd.model import gcn, tree

@@ -1041,7 +1041,11 @@ def _run_full(api, dev, g, c, trees_from="pruner"):
 
 
 @pytest.mark.parametrize("M,D,Tin,H", [(1000, 50, 200, 200), (37, 6, 24, 24), (130, 16, 64, 72), (65, 9, 250, 40), (300, 200, 96, 200),
-                                       (520, 24, 300, 300), (70, 5, 600, 296)])      # hidden 300 = BASELINE configs[4]: Tin > 256, the contraction in runs
+                                       (520, 24, 300, 300), (70, 5, 600, 296),       # hidden 300 = BASELINE configs[4]: Tin > 256, the contraction in runs
+                                       # edges of the helpers both precisions share: one relation, < 16 rows, scalar-tail stores; nd = 2 and one live
+                                       # row / column / two columns in the second tiles; a row past a workgroup, odd D, an odd m-step in dW; the
+                                       # smallest width cut into two runs in both precisions and both orientations
+                                       (5, 1, 8, 6), (17, 2, 33, 18), (257, 3, 40, 50), (20, 2, 264, 264)])
 def test_bilinear_traverse_kernel(api, dev, M, D, Tin, H):
     """gcnpt_bilinear_fwd (bf16 MFMA operands, fp32 accumulate) against the fp32 einsum of the reference's traverse_deprel
     (gcn.py:408-414), and its library-GEMM backward against autograd of that einsum."""
@@ -1083,7 +1087,8 @@ def test_bilinear_traverse_kernel(api, dev, M, D, Tin, H):
 
 
 @pytest.mark.parametrize("M,D,Tin,H", [(1000, 50, 200, 200), (37, 6, 24, 24), (130, 16, 64, 72), (65, 9, 250, 40), (300, 200, 96, 200),
-                                       (520, 24, 300, 300), (70, 5, 600, 296)])
+                                       (520, 24, 300, 300), (70, 5, 600, 296),
+                                       (5, 1, 8, 6), (17, 2, 33, 18), (257, 3, 40, 50), (20, 2, 264, 264)])      # the shared helpers' edges, as above
 def test_bilinear_traverse_kernel_fp32(api, dev, M, D, Tin, H):
     """the traversal contraction (gcn.py:400-415) in EXACT fp32 MFMA (v_mfma_f32_16x16x4_f32), forward and the three
     gradients on the kernels, against the fp32 einsum of the reference's traverse_deprel and its autograd: 1e-5 forward, 1e-4 gradients

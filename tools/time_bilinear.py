@@ -10,7 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gcn_over_pruned_trees_amd import _lib  # noqa: E402
-from gcn_over_pruned_trees_amd.model import gcn  # noqa: E402
+from gcn_over_pruned_trees_amd.model import deprel, gcn  # noqa: E402
 
 
 def timed(fn, n=30):
@@ -38,10 +38,8 @@ def main():
         rec = {}
         for name, cd in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
             code = _lib.dtype_code(cd)
-            k = 32 if cd == torch.bfloat16 else 16
-            img = torch.empty((lib.gcnpt_bilinear_packed_bytes(D, Tin, H, code),), dtype=torch.uint8, device=dev)
-            xb = torch.zeros((M, (Tin + k - 1) // k * k), dtype=cd, device=dev)
-            xb[:, :Tin] = x.detach()
+            img = deprel.image_buffer(lib.gcnpt_bilinear_packed_bytes(D, Tin, H, code), dev)
+            xb = deprel.padded_cols(x.detach(), *deprel.operand_format(code))
             y = torch.empty((lib.gcnpt_bilinear_planes(M, D, Tin, H, code), M, H), device=dev)
             st = _lib.stream()
             Wd, ed = W.detach(), e.detach()
