@@ -10,6 +10,7 @@ Layout
   model/   host-side mirror of the reference's interface for this path
            (model.tree, model.gcn: GCN / GCNRelationModel / GCNClassifier / pool)
   shard.py sentence sharding + flat-bucket gradient all-reduce for data parallel runs
+  optim.py the single-process optimizer step: clip_grad_norm_ + SGD / MyAdagrad + zero_grad as one native call
   utils/   restated constants and the synthetic TACRED-shaped batch generator
 
 Import as `gcn_over_pruned_trees_amd` (alias module at the repo root).

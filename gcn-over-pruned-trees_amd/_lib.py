@@ -30,7 +30,21 @@ class Step(ctypes.Structure):
                 ("gy", _p), ("dh", _p * 8), ("dh_dtype", _i * 8), ("scale", _f * 8), ("z_frag", _p * 8), ("dW", _p * 8), ("db", _p * 8)]
 
 
+class OptimTensor(ctypes.Structure):
+    """gcnpt_optim_tensor_t of include/gcnpt.h: one dense parameter of gcnpt_optim_step."""
+    _fields_ = [("w", _p), ("g", _p), ("state", _p), ("n", _ll)]
+
+
+class OptimTable(ctypes.Structure):
+    """gcnpt_optim_table_t of include/gcnpt.h: one row-sparse parameter of gcnpt_optim_step."""
+    _fields_ = [("w", _p), ("state", _p), ("ids", _p), ("rows", _p), ("owner", _p), ("scratch", _p),
+                ("V", _i), ("E", _i), ("n_rows", _i), ("reserved", _i)]
+
+
 STEP_PACK, STEP_FWD, STEP_BWD = 1, 2, 4         # gcnpt_step_t.parts
+OPTIM_SGD, OPTIM_ADAGRAD = 0, 1                 # gcnpt_optim_step kinds
+OPTIM_NORM, OPTIM_COEF = 0, 1                   # slots of its partials the call leaves the pre-clip norm and the coefficient in
+OPTIM_TENSORS_PER_LAUNCH, OPTIM_TABLES_PER_LAUNCH = 64, 8
 SIGNATURES = {
     "gcnpt_abi_version": (_i, []),
     "gcnpt_last_error": (ctypes.c_char_p, []),
@@ -95,6 +109,8 @@ SIGNATURES = {
     "gcnpt_head_linear_bwd": (_i, [_p, _p, _p, _p, _ll, _p, _p, _ll, _p, _p, _i, _i, _i, _i]),
     "gcnpt_head_loss_fwd": (_i, [_p, _p, _p, _p, _ll, _i, _f, _i, _i, _p, _p, _p, _p]),
     "gcnpt_head_loss_bwd": (_i, [_p, _p, _p, _p, _p, _ll, _i, _f, _i, _i, _p, _p]),
+    "gcnpt_optim_partials_floats": (_sz, [_i, _i]),
+    "gcnpt_optim_step": (_i, [_p, _i, ctypes.POINTER(OptimTensor), _i, ctypes.POINTER(OptimTable), _i, _f, _f, _p, _i, _p]),
 }
 
 

@@ -604,6 +604,60 @@ int gcnpt_head_loss_fwd(void* stream, const float* logits, const int64_t* labels
 int gcnpt_head_loss_bwd(void* stream, const float* dloss, const float* logits, const int64_t* labels, const float* pooled, long long ldp, int H,
                         float l2, int M, int C, float* dlogits, float* dpooled);
 
+/* ---- the single-process optimizer step, reference train.py:225-227: clip_grad_norm_(parameters, max_grad_norm); optimizer.step();
+ * optimizer.zero_grad() -- for torch.optim.SGD and for MyAdagrad (utils/torch_utils.py:10-90 with lr_decay = 0 and weight_decay = 0, the only
+ * way the reference constructs it), on the parameters WHERE THEY LIVE: a list of dense tensors and a list of row-sparse tables.  Everything
+ * float32; sums of squares in double.  With G = the gradient with duplicate ids summed:
+ *     norm = sqrt(sum_dense g^2 + sum_tables |G|^2)         coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1       g^ = coef * g
+ *     GCNPT_OPTIM_SGD:      w -= lr * g^
+ *     GCNPT_OPTIM_ADAGRAD:  state += g^ * g^;  w -= lr * g^ / (sqrt(state) + 1e-10)
+ * and the same per coalesced row of a table.  Rows of a table's w / state that no id names are neither read nor written; ids outside
+ * [0, V) contribute nothing.
+ * gcnpt_optim_tensor_t: one dense parameter.  w, g [dev] float32 [n], n >= 1, any 4-byte alignment (tensors whose w, g and state are all
+ *   16-byte aligned take 16-byte accesses); state [dev] float32 [n], the Adagrad sum (required for GCNPT_OPTIM_ADAGRAD, unused for SGD).
+ *   clear_grads != 0: the update launch stores zeros over every g it consumed (zero_grad without a pass of its own).
+ * gcnpt_optim_table_t: one row-sparse parameter.  w [dev] [V,E] (state alike); ids [dev] int64 [n_rows] and rows [dev] float32 [n_rows,E]:
+ *   the UNCOALESCED gradient, one row per token, duplicate ids allowed (what gcnpt_embed_bwd's d_emb_rows holds).  rows is MODIFIED: no sort --
+ *   one owner token per id is elected with an integer atomic min of the token position into owner[id], every other token's row is added
+ *   into its owner's row of `rows`, and the norm and the update walk owner rows only.  owner [dev] int32 [V] must be all -1 on entry and is
+ *   all -1 again afterwards (only the touched entries are reset; no [V] clear per step); scratch [dev] int32 [n_rows], no initialisation
+ *   needed.  n_rows = 0 is allowed (nothing to do).  n_rows * E and V * E may be anything that fits the pointers' buffers.
+ *   The merge uses float atomic adds (256 contiguous bytes per wave-instruction), so a row that more than two tokens share depends in its
+ *   last bits on arrival order; with GCNPT_OPT_DETERMINISTIC = 1 the owner adds the other tokens' rows one at a time in ascending token
+ *   position, starting from its own: defined bit for bit, O(n_rows^2 / 64) id comparisons.
+ * lr is passed by value; lr_dev [dev] float32 [1], when not NULL, is read by the kernels instead (a captured step follows a decayed lr).
+ * partials [dev] float32 [gcnpt_optim_partials_floats(n_tensors, n_tables)] caller scratch, no initialisation needed; afterwards
+ *   partials[GCNPT_OPTIM_NORM] = the pre-clip norm and partials[GCNPT_OPTIM_COEF] = coef.  The size query is host-only arithmetic.
+ * The descriptor arrays are HOST memory read during the call (like gcnpt_step_t); their pointers travel as kernel arguments,
+ * GCNPT_OPTIM_TENSORS_PER_LAUNCH tensors and GCNPT_OPTIM_TABLES_PER_LAUNCH tables per launch: a model that fits one argument block takes
+ * four launches (two without tables), a larger one more launches per phase.  Checked before any HIP call: NULL w / g / ids / rows / owner /
+ * scratch / partials, n <= 0, E <= 0, V <= 0, negative counts, a pointer that is not 4-byte aligned, an unknown kind, Adagrad without
+ * state, NaN or negative lr / max_norm -> GCNPT_E_INVALID. */
+#define GCNPT_OPTIM_SGD 0
+#define GCNPT_OPTIM_ADAGRAD 1
+#define GCNPT_OPTIM_NORM 0
+#define GCNPT_OPTIM_COEF 1
+#define GCNPT_OPTIM_TENSORS_PER_LAUNCH 64
+#define GCNPT_OPTIM_TABLES_PER_LAUNCH 8
+typedef struct gcnpt_optim_tensor {
+    float* w;
+    float* g;
+    float* state;
+    long long n;
+} gcnpt_optim_tensor_t;
+typedef struct gcnpt_optim_table {
+    float* w;
+    float* state;
+    const int64_t* ids;
+    float* rows;
+    int32_t* owner;
+    int32_t* scratch;
+    int V, E, n_rows, reserved;
+} gcnpt_optim_table_t;
+size_t gcnpt_optim_partials_floats(int n_tensors, int n_tables);
+int gcnpt_optim_step(void* stream, int kind, const gcnpt_optim_tensor_t* tensors, int n_tensors, const gcnpt_optim_table_t* tables,
+                     int n_tables, float max_norm, float lr, const float* lr_dev, int clear_grads, float* partials);
+
 #ifdef __cplusplus
 }
 #endif
