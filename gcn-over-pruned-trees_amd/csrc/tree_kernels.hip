@@ -13,6 +13,7 @@
 //   edges = {(head[i]-1 -> i) : keep[i], i != lca, head[i] > 0}.
 #include "gcnpt_common.h"
 #include "pack_common.h"
+#include "tree_layout.h"
 
 namespace gcnpt {
 
@@ -26,21 +27,22 @@ enum : int {
 enum : int { K_KEEP = 1, K_CHILD = 2 };
 enum : int { ERR_CHAIN_BADHEAD = 1, ERR_CHAIN_CYCLE = 2, ERR_BADHEAD = 4, ERR_CYCLE = 8, ERR_ASSERT = 16 };
 
-// Token-packed output of the pruner (gcnpt_prune_to_csr_packed; layout of gcnpt_pack_trees in include/gcnpt.h): row cu[b] + i, columns
+// the parse of a batch [B, T].  The sentences' lengths: from pad_mask, or (NULL) from the array len [B], which travels beside this
+// struct as a parameter of its own: `const __restrict__` on a kernel parameter is what makes len[b] a scalar load, and a member
+// cannot carry it
+struct ParseSrc {
+    const int64_t *head, *subj_pos, *obj_pos, *deprel;
+    const uint8_t* pad_mask;
+};
+
+// Token-packed output of the pruner (gcnpt_prune_to_csr_packed; a PackedDst with cu != NULL): row cu[b] + i, columns
 // shifted by cu[b], entry offsets contiguous over the batch.  A sentence's offsets are prefix sums of (len, nnz, nnzT) over the sentences
 // before it, which other workgroups of the SAME launch compute: every workgroup publishes its three counts in ONE 8-byte word (valid bit |
 // len << 40 | nnz << 20 | nnzT, an agent-scope atomic store: the word is its own flag, nothing to order), then sums the words of the
 // sentences before it (agent-scope atomic loads, spinning on the valid bit).  Sentences are taken in TICKET order (an atomic counter), not
 // in blockIdx order, so a workgroup only ever waits for workgroups that already run: no assumption about dispatch order.  The last
 // workgroup to finish polling clears the words and both counters: the workspace is all-zero between launches (graph replay included).
-struct PackedOut {
-    int32_t* cu;                 // NULL = the padded layout (everything below unused)
-    int32_t* row_sent;
-    uint8_t* pool_mask_padded;   // NULL or [B*T]: the mask in the padded layout as well (what GCN.forward returns, gcn.py:262,395)
-    unsigned long long* sync;    // [B + 2], zero between launches: the sentences' words, ticket counter, done counter
-    int32_t* pk_status;          // [2]: 0 / GCNPT_E_CAPACITY, sum(len)
-    int n_rows, nnz_cap;
-};
+// sync: [B + 2], zero between launches: the sentences' words, ticket counter, done counter.
 constexpr unsigned long long PK_VALID = 1ull << 63;
 
 // exclusive scan of a[0..n) in place, a[n] = total; `scratch` holds blockDim.x ints (any block size)
@@ -73,25 +75,8 @@ __device__ __forceinline__ int wave_min(int v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
     return v;
 }
-// exclusive scan of a[0..n) in place by ONE wave (lane l owns the contiguous segment l); returns the total
-__device__ __forceinline__ int wave_exclusive_scan(int* a, int n, int lane) {
-    const int seg = (n + WAVE - 1) / WAVE;
-    const int lo = min(n, lane * seg), hi = min(n, lo + seg);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    int inc = s;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const int u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    const int total = __shfl(inc, WAVE - 1);
-    int run = inc - s;
-    for (int i = lo; i < hi; ++i) { const int v = a[i]; a[i] = run; run += v; }
-    return total;
-}
-
-// the same for three arrays at once: three independent shuffle chains share the latency of one
+// exclusive scan of a[0..n), b[0..n), c[0..n) in place by ONE wave (lane l owns the contiguous segment l), the totals in ta, tb, tc:
+// three independent shuffle chains share the latency of one
 __device__ __forceinline__ void wave_exclusive_scan3(int* a, int* b, int* c, int n, int lane, int& ta, int& tb, int& tc) {
     const int seg = (n + WAVE - 1) / WAVE;
     const int lo = min(n, lane * seg), hi = min(n, lo + seg);
@@ -117,6 +102,20 @@ __device__ __forceinline__ void wave_exclusive_scan3(int* a, int* b, int* c, int
 constexpr int PW_SHIFT = 12, PW_MASK = (1 << PW_SHIFT) - 1, PRUNE_MAX_T = PW_MASK - 3;
 __device__ __forceinline__ int pw_par(int w) { return (w & PW_MASK) - 2; }
 
+// One word per row that carries an edge, with everything the row emission needs of it: bits 0..11 = the token, 12..23 = parent + 2 (as
+// in its pw word), 24 = it is a kept child of that parent, 25 / 26 = the entry the pair has in the forward / reverse direction is non-zero.
+constexpr int ER_CHILD = 1 << 24, ER_FWD_NZ = 1 << 25, ER_REV_NZ = 1 << 26;
+__device__ __forceinline__ int er_encode(int token, int pw, int keep_bits) {
+    const int f = pw >> PW_SHIFT;
+    return token | ((pw & PW_MASK) << PW_SHIFT) | ((keep_bits & K_CHILD) ? ER_CHILD : 0) | ((f & F_FWD_NZ) ? ER_FWD_NZ : 0) |
+           ((f & F_REV_NZ) ? ER_REV_NZ : 0);
+}
+__device__ __forceinline__ int er_token(int w) { return w & PW_MASK; }
+__device__ __forceinline__ int er_parent(int w) { return pw_par(w >> PW_SHIFT); }
+__device__ __forceinline__ bool er_is_child(int w) { return w & ER_CHILD; }
+__device__ __forceinline__ bool er_fwd_nz(int w) { return w & ER_FWD_NZ; }
+__device__ __forceinline__ bool er_rev_nz(int w) { return w & ER_REV_NZ; }
+
 // Sentences of up to PRUNE_WAVE0_T tokens: wave 0 runs the pruning phases alone, separated by wave_lds_fence() (gcnpt_common.h): no
 // workgroup barrier.  Longer ones (ALLW): every phase is a loop over the tokens by ALL 1024 threads with a
 // workgroup barrier behind it, so a 300-token sentence is one round per phase instead of five (round 2: 30 us at T = 300).
@@ -125,32 +124,65 @@ __device__ __forceinline__ int pw_par(int w) { return (w & PW_MASK) - 2; }
 #endif
 constexpr int PRUNE_WAVE0_T = GCNPT_PRUNE_WAVE0_T;
 
+// status[B] = longest sentence of the batch (gcn.py:97).  false: waves of workgroup 0 that have no token to prune find it (see the
+// kernel).  true -- batches too big for that, sentences that leave no idle wave --: one atomicMax per sentence, on a word that
+// prune_impl clears in front of the launch.
+__host__ __device__ constexpr bool longest_by_atomic(int B, int T) {
+    return (long long)B * T > PRUNE_SCAN_MAX || (T > PRUNE_WAVE0_T && T + WAVE > PRUNE_THREADS);
+}
+
+// The workgroup's dynamic LDS: PER_TOKEN words per token for the pruning phases, PER_TOKEN_STAGED with the entry lists of the staged
+// row emission (emit_rows), FIXED on top (deg, degT and rank hold T + 1).  Two regions change hands between the phases.
+struct PruneLds {
+    static constexpr int PER_TOKEN = 7, PER_TOKEN_STAGED = 14, FIXED = 4;
+    // (n_long is the LAST word of bytes(T, true): entF starts behind FIXED, so there is no slack word to give away)
+    static constexpr size_t bytes(int T, bool staged) { return sizeof(int) * ((size_t)(staged ? PER_TOKEN_STAGED : PER_TOKEN) * T + FIXED); }
+    int* pw;        // [T]   parent + flags (see above)
+    int* cnt;       // [T]   #entity chains through the token; from the distance phase on the K_KEEP / K_CHILD bits; in the staged
+                    //       emission the fill counter of the forward rows
+    int* deg;       // [T+1] row degree -> row offsets
+    int* degT;      // [T+1] column degree -> transposed row offsets
+    int* rank;      // [T+1] rank of the token among the rows that carry an edge; in the staged emission the fill counter of the transposed rows
+    int* lab;       // [T]   deprel id of the token
+    int* einfo;     // [T]   the edge rows, ascending (er_encode)
+    // staged only
+    int* entF;      // [3T]  forward entries: column (the label follows from the pair, see write_row)
+    int* entT;      // [3T]  transposed entries: column
+    int* longrows;  // [<= T / EMIT_SORT_MAX + 1] edge rows left to the scan form
+    int* n_long;    //       their count: the last word of that region
+    __device__ PruneLds(int* smem, int T)
+        : pw(smem), cnt(pw + T), deg(cnt + T), degT(deg + T + 1), rank(degT + T + 1), lab(rank + T + 1), einfo(lab + T),
+          entF(smem + PER_TOKEN * T + FIXED), entT(entF + 3 * T), longrows(entT + 3 * T), n_long(longrows + T - 1) {}
+};
+
+// The workgroup's static words.
+struct PruneShared {
+    int err;        // ERR_* bits of the phases
+    int status;     // the sentence's GCNPT_E_* code (packed output that does not fit: GCNPT_E_CAPACITY)
+    int nrows;      // rows that carry an edge (0 for a failed sentence)
+    int red[4];     // workgroup-wide sums / minimum of the ALLW form: [0] pad slots, [1] subject tokens, [2] entity tokens, [3] lca;
+                    // then the three sums of the look-back
+    int out[4];     // padded: first row, first entry of the two patterns, column shift; packed: len, nnz, nnzT until the look-back
+    int ticket;     // the sentence this workgroup takes
+    int maxlen;     // workgroup 0: the longest sentence
+};
+
 // Phases: lengths, LCA, path, distances, kept tokens, degrees, row offsets, compacted edge rows.
-// s_red: [0] pad slots, [1] subject tokens, [2] entity tokens, [3] lca (workgroup-wide sums / minimum of the ALLW form)
+// (dst by reference here and in emit_rows / emit_row_scan: measured against a copy, the packed shapes are 0.1 us faster.)
 template <bool ALLW>
-__device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* __restrict__ subj_pos,
-                               const int64_t* __restrict__ obj_pos, const int64_t* __restrict__ deprel,
-                               const uint8_t* __restrict__ pad_mask, const int32_t* __restrict__ len_in, int b, int B, int T,
-                               int prune_k, int cap, int* smem, int* s_err, int* s_status, int* s_nrows, int* s_red,
-                               int32_t* __restrict__ row_ptr, int32_t* __restrict__ rowT_ptr, int32_t* __restrict__ ell,
-                               int32_t* __restrict__ ellT, uint8_t* __restrict__ pool_mask, int32_t* __restrict__ status,
-                               unsigned long long* stamps, const PackedOut& po, int* s_out) {
-    int* pw = smem;                // [T]   parent + flags (see above)
-    int* cnt = pw + T;             // [T]   #entity chains through the token; later K_KEEP/K_CHILD bits
-    int* deg = cnt + T;            // [T+1] row degree -> row offsets
-    int* degT = deg + T + 1;       // [T+1] column degree -> transposed row offsets
-    int* rank = degT + T + 1;      // [T+1] rank of the token among the rows that carry an edge
-    int* lab = rank + T + 1;       // [T]   deprel id of the token
-    int* einfo = lab + T;          // [T]   compacted edge rows: token | (parent+2) << 12 | child/label bits << 24
+__device__ void prune_sentence(const ParseSrc in, const int32_t* __restrict__ len_in, int b, int B, int T, int prune_k, int cap,
+                               const PruneLds L, PruneShared& sh, const PackedDst& dst, unsigned long long* sync,
+                               unsigned long long* stamps) {
+    int *const pw = L.pw, *const cnt = L.cnt, *const deg = L.deg, *const degT = L.degT, *const rank = L.rank;
     const int lane = threadIdx.x & 63;
     const int t0 = ALLW ? (int)threadIdx.x : lane;            // this thread's first token
     constexpr int NT = ALLW ? PRUNE_THREADS : WAVE;           // token stride
     const size_t base = (size_t)b * T;
     auto phase_sync = [&]() { if constexpr (ALLW) __syncthreads(); else wave_lds_fence(); };
-    // sum over the participating threads (ALLW: through s_red[slot], which the kernel cleared; the caller syncs before reading)
+    // sum over the participating threads (ALLW: through sh.red[slot], which the kernel cleared; the caller syncs before reading)
     auto team_sum = [&](int v, int slot) {
         v = wave_sum(v);
-        if constexpr (ALLW) { if (lane == 0 && v) atomicAdd(&s_red[slot], v); }
+        if constexpr (ALLW) { if (lane == 0 && v) atomicAdd(&sh.red[slot], v); }
         return v;
     };
 
@@ -165,8 +197,8 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
             const size_t j = base + min(i0 + u * NT + t0, T - 1);
-            h[u] = head[j]; sp[u] = subj_pos[j]; op[u] = obj_pos[j]; d[u] = deprel[j];
-            pad[u] = pad_mask ? pad_mask[j] != 0 : false;
+            h[u] = in.head[j]; sp[u] = in.subj_pos[j]; op[u] = in.obj_pos[j]; d[u] = in.deprel[j];
+            pad[u] = in.pad_mask ? in.pad_mask[j] != 0 : false;
         }
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
@@ -180,20 +212,18 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
             if (d[u] + FWD_BOUND != 0) f |= F_REV_NZ;      // adj[c,p] = deprel[c] + 42
             const int p = h[u] > 0 ? (int)min(h[u] - 1, (int64_t)(PW_MASK - 2)) : -1;      // range-checked against len below
             pw[i] = (p + 2) | (f << PW_SHIFT);
-            lab[i] = (int)d[u]; cnt[i] = 0; deg[i] = 0; degT[i] = 0;
+            L.lab[i] = (int)d[u]; cnt[i] = 0; deg[i] = 0; degT[i] = 0;
         }
     }
     // sentence length = number of non-pad slots (gcn.py:96)
     int len;
-    if (pad_mask) {
+    if (in.pad_mask) {
         const int np = team_sum(npad, 0);
-        if constexpr (ALLW) { __syncthreads(); len = T - s_red[0]; } else { len = T - np; }
+        if constexpr (ALLW) { __syncthreads(); len = T - sh.red[0]; } else { len = T - np; }
     } else {
         len = min(max(len_in[b], 0), T);
     }
-    // (the longest sentence: workgroup 0's idle waves scan for it, see the kernel; batches too big for that / sentences that leave no
-    // idle wave: one atomicMax per sentence on a word prune_impl cleared)
-    if (threadIdx.x == 0 && ((long long)B * T > PRUNE_SCAN_MAX || (ALLW && T + WAVE > PRUNE_THREADS))) atomicMax(&status[B], len);
+    if (threadIdx.x == 0 && longest_by_atomic(B, T)) atomicMax(&dst.sent_status[B], len);
     int nsubj = 0, nent = 0;
     for (int i = t0; i < T; i += NT) {
         const int w = pw[i];
@@ -207,7 +237,7 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
     nsubj = team_sum(nsubj, 1);
     nent = team_sum(nent, 2);
     phase_sync();
-    if constexpr (ALLW) { nsubj = s_red[1]; nent = s_red[2]; }
+    if constexpr (ALLW) { nsubj = sh.red[1]; nent = sh.red[2]; }
     GCNPT_STAMP(stamps, 1);
 
     // ---- every entity token walks to the root, counting visits (tree.py:86-109)
@@ -219,14 +249,14 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
         while (a >= 0) {
             atomicAdd(&cnt[a], w);                     // result unused: no-return LDS add, nothing to wait for
             a = pw_par(pw[a]);
-            if (++steps > len) { atomicOr(s_err, ERR_CHAIN_CYCLE); a = -1; }
+            if (++steps > len) { atomicOr(&sh.err, ERR_CHAIN_CYCLE); a = -1; }
         }
-        if (a == -2) atomicOr(s_err, ERR_CHAIN_BADHEAD);
+        if (a == -2) atomicOr(&sh.err, ERR_CHAIN_BADHEAD);
     }
     phase_sync();
     int err = 0;
-    if (*s_err & ERR_CHAIN_BADHEAD) err = GCNPT_E_BAD_HEAD;
-    else if (*s_err & ERR_CHAIN_CYCLE) err = GCNPT_E_CYCLE;
+    if (sh.err & ERR_CHAIN_BADHEAD) err = GCNPT_E_BAD_HEAD;
+    else if (sh.err & ERR_CHAIN_CYCLE) err = GCNPT_E_CYCLE;
     else if (nsubj == 0) err = GCNPT_E_NO_SUBJECT;
     GCNPT_STAMP(stamps, 2);
 
@@ -245,9 +275,9 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
             if (((pw[i] >> PW_SHIFT) & (F_CA | F_CA_HASCHILD)) == F_CA) lca = min(lca, i);
         lca = wave_min(lca);
         if constexpr (ALLW) {
-            if (lane == 0 && lca != 0x7fffffff) atomicMin(&s_red[3], lca);
+            if (lane == 0 && lca != 0x7fffffff) atomicMin(&sh.red[3], lca);
             __syncthreads();
-            lca = s_red[3];
+            lca = sh.red[3];
         }
         if (lca == 0x7fffffff) err = GCNPT_E_NO_LCA;
     }
@@ -263,16 +293,16 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
             while (a >= 0 && !(w & (F_PATH << PW_SHIFT))) {          // one LDS read per step
                 a = pw_par(w);
                 if (a >= 0) w = pw[a];
-                if (++d > len) { atomicOr(s_err, ERR_CYCLE); a = -1; }
+                if (++d > len) { atomicOr(&sh.err, ERR_CYCLE); a = -1; }
             }
-            if (a == -2) atomicOr(s_err, ERR_BADHEAD);
+            if (a == -2) atomicOr(&sh.err, ERR_BADHEAD);
             const bool keep = a >= 0 && d <= prune_k;
             const bool child = keep && i != lca && pw_par(pw[i]) >= 0;
             cnt[i] = (keep ? K_KEEP : 0) | (child ? K_CHILD : 0);   // cnt is free from here on
         }
         phase_sync();
-        if (*s_err & ERR_BADHEAD) err = GCNPT_E_BAD_HEAD;
-        else if (*s_err & ERR_CYCLE) err = GCNPT_E_CYCLE;
+        if (sh.err & ERR_BADHEAD) err = GCNPT_E_BAD_HEAD;
+        else if (sh.err & ERR_CYCLE) err = GCNPT_E_CYCLE;
     }
     GCNPT_STAMP(stamps, 4);
 
@@ -281,14 +311,14 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
         for (int i = t0; i < len; i += NT) {
             if (!(cnt[i] & K_CHILD)) continue;
             const int w = pw[i], p = pw_par(w), f = w >> PW_SHIFT;
-            if (!(cnt[p] & K_KEEP)) atomicOr(s_err, ERR_ASSERT);   // tree.py:159
+            if (!(cnt[p] & K_KEEP)) atomicOr(&sh.err, ERR_ASSERT);   // tree.py:159
             if (f & F_FWD_NZ) { atomicAdd(&deg[p], 1); atomicAdd(&degT[i], 1); }
             if (f & F_REV_NZ) { atomicAdd(&deg[i], 1); atomicAdd(&degT[p], 1); }
             atomicOr(&pw[p], F_HASEDGE << PW_SHIFT);
             atomicOr(&pw[i], F_HASEDGE << PW_SHIFT);
         }
         phase_sync();
-        if (*s_err & ERR_ASSERT) err = GCNPT_E_ASSERT;
+        if (sh.err & ERR_ASSERT) err = GCNPT_E_ASSERT;
     }
     int n_edge_rows = 0;
     if (!err) {
@@ -296,8 +326,7 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
             const int he = (i < len && (pw[i] & (F_HASEDGE << PW_SHIFT))) ? 1 : 0;
             deg[i] += he; degT[i] += he;                             // the 84 on the diagonal
             rank[i] = he;
-            uint8_t* pm = po.cu ? po.pool_mask_padded : pool_mask;
-            if (pm) pm[base + i] = (deg[i] + degT[i]) == 0;                      // gcn.py:262
+            if (dst.pool_mask_padded) dst.pool_mask_padded[base + i] = (deg[i] + degT[i]) == 0;      // gcn.py:262
         }
         phase_sync();
         if (!ALLW || threadIdx.x < WAVE) {                           // the three scans: one wave (lane l owns a contiguous segment)
@@ -311,116 +340,100 @@ __device__ void prune_sentence(const int64_t* __restrict__ head, const int64_t* 
     }
     GCNPT_STAMP(stamps, 5);
 
-    // ---- where this sentence's rows and entries go.  Padded layout: slots of its own (rows b*T.., entries b*cap..).  Packed: behind
-    //      the sentences before it (see PackedOut): the counts are published HERE, the offsets are taken as late as possible -- in
-    //      emit_rows(), after the rows have been sorted in registers --, so that waiting for a slower sentence costs nothing
-    const size_t rbase = base;              // first row
-    const int ebase = b * cap, eTbase = b * cap;   // first entry of the two patterns
-    if (po.cu) {
+    // ---- where this sentence's rows and entries go.  Padded layout: slots of its own (rows b*T.., entries b*cap..), its T + 1 row
+    //      offsets from b*(T+1).  Packed: behind the sentences before it (see PK_VALID): the counts are published HERE, the offsets
+    //      are taken as late as possible -- in emit_rows(), after the rows have been sorted in registers --, so that waiting for a
+    //      slower sentence costs nothing
+    const bool packed = dst.cu != nullptr;
+    if (packed) {
         const int my_nnz = err ? 0 : deg[T], my_nnzT = err ? 0 : degT[T];
         if (threadIdx.x == 0) {
-            __hip_atomic_store(po.sync + b, PK_VALID | ((unsigned long long)len << 40) | ((unsigned long long)my_nnz << 20) | (unsigned long long)my_nnzT,
+            __hip_atomic_store(sync + b, PK_VALID | ((unsigned long long)len << 40) | ((unsigned long long)my_nnz << 20) | (unsigned long long)my_nnzT,
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_out[0] = len; s_out[1] = my_nnz; s_out[2] = my_nnzT;
-            status[b] = err; *s_status = err; *s_nrows = err ? 0 : n_edge_rows;
+            sh.out[0] = len; sh.out[1] = my_nnz; sh.out[2] = my_nnzT;
+            dst.sent_status[b] = err; sh.status = err; sh.nrows = err ? 0 : n_edge_rows;
         }
-        if (err) {
-            if (po.pool_mask_padded)
-                for (int i = t0; i < T; i += NT) po.pool_mask_padded[base + i] = 1;
+        if (err) {                                                   // (its rows are written in emit_rows)
+            if (dst.pool_mask_padded)
+                for (int i = t0; i < T; i += NT) dst.pool_mask_padded[base + i] = 1;
             return;
         }
         for (int i = t0; i < len; i += NT) {                         // the compacted edge rows (see below); every global write waits
             const int w = pw[i];
-            if (w & (F_HASEDGE << PW_SHIFT)) {
-                const int f = w >> PW_SHIFT;
-                einfo[rank[i]] = i | ((w & PW_MASK) << 12) | ((cnt[i] & K_CHILD) ? 1 << 24 : 0) |
-                                 ((f & F_FWD_NZ) ? 1 << 25 : 0) | ((f & F_REV_NZ) ? 1 << 26 : 0);
-            }
+            if (w & (F_HASEDGE << PW_SHIFT)) L.einfo[rank[i]] = er_encode(i, w, cnt[i]);
         }
         if constexpr (!ALLW) wave_lds_fence();
         GCNPT_STAMP(stamps, 6);
         return;
     }
-    // row_ptr index of this sentence's row 0 (the padded layout keeps T + 1 offsets per sentence)
+    const int ebase = b * cap;
     const size_t rp0 = (size_t)b * (T + 1);
-    const int n_off = T + 1;
-    if (threadIdx.x == 0) { s_out[0] = (int)rbase; s_out[1] = ebase; s_out[2] = eTbase; s_out[3] = 0; }
+    if (threadIdx.x == 0) { sh.out[0] = (int)base; sh.out[1] = ebase; sh.out[2] = ebase; sh.out[3] = 0; }
 
     if (err) {   // the sentence contributes no edges; every row is empty and masked
-        for (int i = t0; i < n_off; i += NT) {
-            row_ptr[rp0 + i] = ebase;
-            if (rowT_ptr) rowT_ptr[rp0 + i] = eTbase;
+        for (int i = t0; i < T + 1; i += NT) {
+            dst.row_ptr[rp0 + i] = ebase;
+            if (dst.rowT_ptr) dst.rowT_ptr[rp0 + i] = ebase;
         }
-        for (int i = t0; i < T; i += NT)
-            if (pool_mask) pool_mask[base + i] = 1;
-        for (int i = t0; i < T * 8; i += NT) {
-            ell[rbase * 8 + i] = 0;
-            if (ellT) ellT[rbase * 8 + i] = 0;
+        for (int i = t0; i < T; i += NT) {
+            if (dst.pool_mask_padded) dst.pool_mask_padded[base + i] = 1;
+            zero_ell_head(base + i, dst.ell, dst.ellT);
         }
-        if (threadIdx.x == 0) { status[b] = err; *s_status = err; }
+        if (threadIdx.x == 0) { dst.sent_status[b] = err; sh.status = err; }
         return;
     }
 
     // ---- emit both patterns, columns ascending (same order a dense -> CSR conversion gives).
     // Only rows that carry an edge have entries, and only such rows appear as columns: compact them (ascending)
     // with everything the inner loop needs in ONE word, so that loop is a stream of broadcast LDS reads.
-    for (int i = t0; i < n_off; i += NT) {
-        row_ptr[rp0 + i] = ebase + deg[i];
-        if (rowT_ptr) rowT_ptr[rp0 + i] = eTbase + degT[i];
+    for (int i = t0; i < T + 1; i += NT) {
+        dst.row_ptr[rp0 + i] = ebase + deg[i];
+        if (dst.rowT_ptr) dst.rowT_ptr[rp0 + i] = ebase + degT[i];
     }
     for (int i = t0; i < T; i += NT) {
         const int w = i < len ? pw[i] : 0;
-        if (w & (F_HASEDGE << PW_SHIFT)) {
-            const int f = w >> PW_SHIFT;
-            einfo[rank[i]] = i | ((w & PW_MASK) << 12) | ((cnt[i] & K_CHILD) ? 1 << 24 : 0) |
-                             ((f & F_FWD_NZ) ? 1 << 25 : 0) | ((f & F_REV_NZ) ? 1 << 26 : 0);
-        } else {                                                     // no entries: an all-zero ELL head
-            int4* e = reinterpret_cast<int4*>(ell + (rbase + i) * 8);
-            e[0] = make_int4(0, 0, 0, 0); e[1] = make_int4(0, 0, 0, 0);
-            if (ellT) {
-                int4* eT = reinterpret_cast<int4*>(ellT + (rbase + i) * 8);
-                eT[0] = make_int4(0, 0, 0, 0); eT[1] = make_int4(0, 0, 0, 0);
-            }
-        }
+        if (w & (F_HASEDGE << PW_SHIFT)) L.einfo[rank[i]] = er_encode(i, w, cnt[i]);
+        else zero_ell_head(base + i, dst.ell, dst.ellT);              // no entries
     }
     if constexpr (!ALLW) wave_lds_fence();                          // (ALLW: the kernel's barrier in front of emit_rows)
     GCNPT_STAMP(stamps, 6);
-    if (threadIdx.x == 0) { *s_nrows = n_edge_rows; status[b] = 0; }
+    if (threadIdx.x == 0) { sh.nrows = n_edge_rows; dst.sent_status[b] = 0; }
 }
 
 // One row of both patterns by ONE WAVE: one candidate column per lane (the edge rows, ascending), ballot + prefix popcount give every
-// entry its slot -- no sorting, any number of entries.  rw / rdeg / rdegT / rlab: the chunk's row info in the lanes' registers (row qq of
-// the chunk is read with v_readlane).
-__device__ __forceinline__ void emit_row_scan(size_t base, int ebase, int eTbase, int cshift, const int* lab, const int* einfo, int n_edge_rows, int lane, int me, int labr_raw,
-                                              int o_rel, int oT_rel, int32_t* __restrict__ col_idx, int32_t* __restrict__ label,
-                                              int32_t* __restrict__ colT_idx, int32_t* __restrict__ ell, int32_t* __restrict__ ellT) {
+// entry its slot -- no sorting, any number of entries.  me: the row's edge-row word; labr_raw, o_rel, oT_rel: its lab / deg / degT (the
+// chunked caller holds them in the lanes' registers and reads row qq of the chunk with v_readlane); base, ebase, eTbase, cshift: where
+// the sentence's rows and entries go (emit_rows).
+__device__ __forceinline__ void emit_row_scan(const PruneLds L, int n_edge_rows, size_t base, int ebase, int eTbase, int cshift, int me,
+                                              int labr_raw, int o_rel, int oT_rel, const PackedDst& dst) {
+    const int lane = threadIdx.x & 63;
     const unsigned long long lt = (1ull << lane) - 1ull;
-    const int r = me & 0xfff, rp = ((me >> 12) & 0xfff) - 2;
-    const bool rchild = me & (1 << 24), rfwd = me & (1 << 25), rrev = me & (1 << 26);
+    const int r = er_token(me), rp = er_parent(me);
+    const bool rchild = er_is_child(me), rfwd = er_fwd_nz(me), rrev = er_rev_nz(me);
     const int labr = labr_raw + FWD_BOUND;
     const int o = ebase + o_rel, oT = eTbase + oT_rel;
-    int32_t* hd = ell + (base + r) * 8;                       // ELL head: [0] = count, [1..7] = first 7 columns
-    int32_t* hdT = ellT ? ellT + (base + r) * 8 : nullptr;
+    int32_t* hd = dst.ell + (base + r) * 8;                   // ELL head: [0] = count, [1..7] = first 7 columns
+    int32_t* hdT = dst.ellT ? dst.ellT + (base + r) * 8 : nullptr;
     int n_e = 0, n_eT = 0;
     for (int k0 = 0; k0 < n_edge_rows; k0 += WAVE) {          // candidate columns: the edge rows, ascending
         const bool valid = k0 + lane < n_edge_rows;
-        const int w = valid ? einfo[k0 + lane] : 0;
-        const int j = w & 0xfff, jp = ((w >> 12) & 0xfff) - 2;
-        const bool is_child = valid && (w & (1 << 24)) && jp == r;      // j is a kept child of r
+        const int w = valid ? L.einfo[k0 + lane] : 0;
+        const int j = er_token(w);
+        const bool is_child = valid && er_is_child(w) && er_parent(w) == r;      // j is a kept child of r
         const bool is_self = valid && j == r;
         const bool is_par = valid && rchild && j == rp;
-        const bool e = (is_child && (w & (1 << 25))) || is_self || (is_par && rrev);      // adj[r,j] != 0
-        const bool eT = (is_child && (w & (1 << 26))) || is_self || (is_par && rfwd);     // adj[j,r] != 0
+        const bool e = (is_child && er_fwd_nz(w)) || is_self || (is_par && rrev);      // adj[r,j] != 0
+        const bool eT = (is_child && er_rev_nz(w)) || is_self || (is_par && rfwd);     // adj[j,r] != 0
         const unsigned long long m = __ballot(e), mT = __ballot(eT);
         if (e) {
             const int pos = n_e + __popcll(m & lt);
-            col_idx[o + pos] = j + cshift;
-            if (label) label[o + pos] = is_self ? SELF_LOOP_ID : (is_child ? lab[j] : labr);
+            dst.col_idx[o + pos] = j + cshift;
+            if (dst.label) dst.label[o + pos] = is_self ? SELF_LOOP_ID : (is_child ? L.lab[j] : labr);
             if (pos < 7) hd[1 + pos] = j + cshift;
         }
         if (eT) {
             const int pos = n_eT + __popcll(mT & lt);
-            if (colT_idx) colT_idx[oT + pos] = j + cshift;
+            if (dst.colT_idx) dst.colT_idx[oT + pos] = j + cshift;
             if (hdT && pos < 7) hdT[1 + pos] = j + cshift;
         }
         n_e += __popcll(m);
@@ -439,92 +452,61 @@ __device__ __forceinline__ void emit_row_scan(size_t base, int ebase, int eTbase
 // ELL head.  Rows with more than EMIT_SORT_MAX entries (a star-shaped parse) go to the scan form below, one wave each.
 // Otherwise: one row at a time per wave, one candidate column per lane (emit_row_scan) -- O(rows^2 / 64) wave iterations, which at
 // T = 300, K = 2 was 11-25 k cycles of the sentence's 29-43 k.
+// Token-packed output: the sentence's offsets are resolved INSIDE it.
 constexpr int EMIT_SORT_MAX = 12;
-// What emit_rows() needs beyond the entry arrays when the output is token-packed: the sentence's offsets are resolved INSIDE it.
-struct PackedEmit {
-    PackedOut po;
-    int b, B;
-    int32_t *row_ptr, *rowT_ptr, *status;
-    uint8_t* pool_mask;
-    int *s_red, *s_status;
-};
-__device__ void emit_rows(int* s_out, int T, int* smem, int err, int n_edge_rows, int lane, int wave, bool staged,
-                          int32_t* __restrict__ col_idx, int32_t* __restrict__ label, int32_t* __restrict__ colT_idx,
-                          int32_t* __restrict__ ell, int32_t* __restrict__ ellT, unsigned long long* stamps, const PackedEmit& pe) {
-    const bool packed = pe.po.cu != nullptr;
+__device__ void emit_rows(const PruneLds L, PruneShared& sh, int b, int B, int T, bool staged, const PackedDst& dst,
+                          unsigned long long* sync, unsigned long long* stamps) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int err = sh.status, n_edge_rows = sh.nrows;
+    const bool packed = dst.cu != nullptr;
     if (err && !packed) return;
     GCNPT_STAMP(stamps, 8);
-    int* cnt = smem + T;               // free after the pruning phases: fill counter of the forward rows
-    int* deg = smem + 2 * T;
-    int* degT = deg + T + 1;
-    int* rank = degT + T + 1;          // free as well: fill counter of the transposed rows
-    int* lab = rank + T + 1;
-    int* einfo = lab + T;
-    size_t base = (size_t)s_out[0];                        // first row, first entries of the two patterns, column shift (prune_sentence)
-    int ebase = s_out[1], eTbase = s_out[2], cshift = s_out[3];
+    int *const cnt = L.cnt, *const deg = L.deg, *const degT = L.degT, *const rank = L.rank;      // (cnt, rank: the fill counters)
+    size_t base = (size_t)sh.out[0];                       // first row, first entries of the two patterns, column shift (prune_sentence)
+    int ebase = sh.out[1], eTbase = sh.out[2], cshift = sh.out[3];
     int done = -1;                                         // (thread 0, packed) how many workgroups had resolved before this one
 
-    // Token-packed output: the look-back of PackedOut.  Sums the words of the sentences before this one (spinning on their valid bits),
+    // Token-packed output: the look-back (see PK_VALID).  Sums the words of the sentences before this one (spinning on their valid bits),
     // then writes everything of the sentence that is not an entry of an edge row: cu, row offsets, empty ELL heads, masks, sentence ids.
     // All threads; false = the sentence does not fit the caller's arrays (nothing of it is written: gcnpt_pack_trees' rule).
     auto resolve = [&]() -> bool {
-        const PackedOut& po = pe.po;
-        const int b = pe.b, B = pe.B;
-        const int len = s_out[0], my_nnz = s_out[1], my_nnzT = s_out[2];
+        const int len = sh.out[0], my_nnz = sh.out[1], my_nnzT = sh.out[2];
         int a0 = 0, a1 = 0, a2 = 0;
         for (int j = threadIdx.x; j < b; j += PRUNE_THREADS) {
-            unsigned long long v = __hip_atomic_load(po.sync + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned long long v = __hip_atomic_load(sync + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             while (!(v & PK_VALID)) {
                 __builtin_amdgcn_s_sleep(2);
-                v = __hip_atomic_load(po.sync + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                v = __hip_atomic_load(sync + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             a0 += (int)((v >> 40) & 0xffff); a1 += (int)((v >> 20) & 0xfffff); a2 += (int)(v & 0xfffff);
         }
         a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-        __syncthreads();                                               // (s_out and the sums of the pruning phases are consumed)
-        if (threadIdx.x == 0) { pe.s_red[0] = 0; pe.s_red[1] = 0; pe.s_red[2] = 0; }
+        __syncthreads();                                               // (sh.out and the sums of the pruning phases are consumed)
+        if (threadIdx.x == 0) { sh.red[0] = 0; sh.red[1] = 0; sh.red[2] = 0; }
         __syncthreads();
-        if (lane == 0 && (a0 | a1 | a2)) { atomicAdd(&pe.s_red[0], a0); atomicAdd(&pe.s_red[1], a1); atomicAdd(&pe.s_red[2], a2); }
+        if (lane == 0 && (a0 | a1 | a2)) { atomicAdd(&sh.red[0], a0); atomicAdd(&sh.red[1], a1); atomicAdd(&sh.red[2], a2); }
         __syncthreads();
-        a0 = pe.s_red[0]; a1 = pe.s_red[1]; a2 = pe.s_red[2];
+        a0 = sh.red[0]; a1 = sh.red[1]; a2 = sh.red[2];
         // this workgroup has polled every sentence before it: the last one to get here leaves the workspace zeroed (finish(), below; the
         // counter's old value is only looked at there, so its round trip is off the sentence's critical path)
-        if (threadIdx.x == 0) done = (int)atomicAdd(po.sync + B + 1, 1ull);
+        if (threadIdx.x == 0) done = (int)atomicAdd(sync + B + 1, 1ull);
         base = (size_t)a0; ebase = a1; eTbase = a2; cshift = a0;
-        const bool fits = a0 + len <= po.n_rows && a1 + my_nnz <= po.nnz_cap && a2 + my_nnzT <= po.nnz_cap;
-        if (threadIdx.x == 0) {
-            po.cu[b] = a0;
-            if (b == B - 1) {                                          // the totals: the one writer of the batch-level results
-                po.cu[B] = a0 + len;
-                po.pk_status[0] = fits ? 0 : GCNPT_E_CAPACITY;         // (offsets grow with b: the last sentence fits iff all do)
-                po.pk_status[1] = a0 + len;
-                if (fits) {
-                    pe.row_ptr[a0 + len] = a1 + my_nnz;
-                    if (pe.rowT_ptr) pe.rowT_ptr[a0 + len] = a2 + my_nnzT;
-                }
-            }
-            if (!fits) *pe.s_status = GCNPT_E_CAPACITY;
+        if (!write_packed_header(b, B, a0, a1, a2, len, my_nnz, my_nnzT, dst.cu, dst.row_ptr, dst.rowT_ptr, dst.status, dst.n_rows, dst.nnz_cap)) {
+            if (threadIdx.x == 0) sh.status = GCNPT_E_CAPACITY;
+            return false;
         }
-        if (!fits) return false;
         for (int i = threadIdx.x; i < len; i += PRUNE_THREADS) {
-            po.row_sent[a0 + i] = b;
-            pe.row_ptr[a0 + i] = a1 + (err ? 0 : deg[i]);
-            if (pe.rowT_ptr) pe.rowT_ptr[a0 + i] = a2 + (err ? 0 : degT[i]);
-            if (pe.pool_mask) pe.pool_mask[a0 + i] = err ? 1 : ((deg[i + 1] - deg[i]) + (degT[i + 1] - degT[i])) == 0;
-            if (err || !(smem[i] & (F_HASEDGE << PW_SHIFT))) {         // no entries: an all-zero ELL head
-                int4* e = reinterpret_cast<int4*>(ell + (size_t)(a0 + i) * 8);
-                e[0] = make_int4(0, 0, 0, 0); e[1] = make_int4(0, 0, 0, 0);
-                if (ellT) {
-                    int4* eT = reinterpret_cast<int4*>(ellT + (size_t)(a0 + i) * 8);
-                    eT[0] = make_int4(0, 0, 0, 0); eT[1] = make_int4(0, 0, 0, 0);
-                }
-            }
+            dst.row_sent[a0 + i] = b;
+            dst.row_ptr[a0 + i] = a1 + (err ? 0 : deg[i]);
+            if (dst.rowT_ptr) dst.rowT_ptr[a0 + i] = a2 + (err ? 0 : degT[i]);
+            if (dst.pool_mask) dst.pool_mask[a0 + i] = err ? 1 : ((deg[i + 1] - deg[i]) + (degT[i + 1] - degT[i])) == 0;
+            if (err || !(L.pw[i] & (F_HASEDGE << PW_SHIFT))) zero_ell_head(a0 + i, dst.ell, dst.ellT);
         }
         return true;
     };
     auto finish = [&]() {
-        if (packed && threadIdx.x == 0 && done == pe.B - 1)
-            for (int j = 0; j < pe.B + 2; ++j) pe.po.sync[j] = 0ull;
+        if (packed && threadIdx.x == 0 && done == B - 1)
+            for (int j = 0; j < B + 2; ++j) sync[j] = 0ull;
     };
     if (err) {                                                         // (packed) an empty sentence still has its rows
         resolve();
@@ -533,26 +515,22 @@ __device__ void emit_rows(int* s_out, int T, int* smem, int err, int n_edge_rows
     }
 
     if (staged && (n_edge_rows > WAVE || packed)) {          // (up to 64 edge rows the scan form is as fast: 4.7 k against 5.3 k cycles at T = 100, K = 1)
-        int* entF = einfo + T;         // [nnz]  forward entries: column (the label follows from the pair, see below)
-        int* entT = entF + 3 * T;      // [nnzT] transposed entries: column
-        int* longrows = entT + 3 * T;  // [<= T / EMIT_SORT_MAX + 1] edge rows left to the scan form; [T-1] (end of the region) = their count
-        int* n_long = longrows + T - 1;
         for (int i = threadIdx.x; i < T; i += PRUNE_THREADS) { cnt[i] = 0; rank[i] = 0; }
-        if (threadIdx.x == 0) *n_long = 0;
+        if (threadIdx.x == 0) *L.n_long = 0;
         __syncthreads();
         for (int q = threadIdx.x; q < n_edge_rows; q += PRUNE_THREADS) {
-            const int me = einfo[q];
-            const int r = me & 0xfff, rp = ((me >> 12) & 0xfff) - 2;
-            entF[deg[r] + atomicAdd(&cnt[r], 1)] = r;                                               // adj[r,r] = 84 (tree.py:186-187)
-            entT[degT[r] + atomicAdd(&rank[r], 1)] = r;
-            if (me & (1 << 24)) {                                                                   // r is a kept child of rp
-                if (me & (1 << 25)) {                                                               // adj[rp,r] = deprel[r]
-                    entF[deg[rp] + atomicAdd(&cnt[rp], 1)] = r;
-                    entT[degT[r] + atomicAdd(&rank[r], 1)] = rp;
+            const int me = L.einfo[q];
+            const int r = er_token(me), rp = er_parent(me);
+            L.entF[deg[r] + atomicAdd(&cnt[r], 1)] = r;                                             // adj[r,r] = 84 (tree.py:186-187)
+            L.entT[degT[r] + atomicAdd(&rank[r], 1)] = r;
+            if (er_is_child(me)) {                                                                  // r is a kept child of rp
+                if (er_fwd_nz(me)) {                                                                // adj[rp,r] = deprel[r]
+                    L.entF[deg[rp] + atomicAdd(&cnt[rp], 1)] = r;
+                    L.entT[degT[r] + atomicAdd(&rank[r], 1)] = rp;
                 }
-                if (me & (1 << 26)) {                                                               // adj[r,rp] = deprel[r] + 42
-                    entF[deg[r] + atomicAdd(&cnt[r], 1)] = rp;
-                    entT[degT[rp] + atomicAdd(&rank[rp], 1)] = r;
+                if (er_rev_nz(me)) {                                                                // adj[r,rp] = deprel[r] + 42
+                    L.entF[deg[r] + atomicAdd(&cnt[r], 1)] = rp;
+                    L.entT[degT[rp] + atomicAdd(&rank[rp], 1)] = r;
                 }
             }
         }
@@ -562,13 +540,13 @@ __device__ void emit_rows(int* s_out, int T, int* smem, int err, int n_edge_rows
         // before it waits with its rows sorted
         struct Row { int r, o, n, oT, nT; int v[EMIT_SORT_MAX], vT[EMIT_SORT_MAX]; };
         auto sort_row = [&](int q, Row& w) -> bool {
-            w.r = einfo[q] & 0xfff;
+            w.r = er_token(L.einfo[q]);
             w.o = deg[w.r]; w.n = deg[w.r + 1] - w.o; w.oT = degT[w.r]; w.nT = degT[w.r + 1] - w.oT;
-            if (w.n > EMIT_SORT_MAX || w.nT > EMIT_SORT_MAX) { longrows[atomicAdd(n_long, 1)] = q; return false; }
+            if (w.n > EMIT_SORT_MAX || w.nT > EMIT_SORT_MAX) { L.longrows[atomicAdd(L.n_long, 1)] = q; return false; }
 #pragma unroll
             for (int k = 0; k < EMIT_SORT_MAX; ++k) {
-                w.v[k] = k < w.n ? entF[w.o + k] : 0x7fffffff;
-                w.vT[k] = k < w.nT ? entT[w.oT + k] : 0x7fffffff;
+                w.v[k] = k < w.n ? L.entF[w.o + k] : 0x7fffffff;
+                w.vT[k] = k < w.nT ? L.entT[w.oT + k] : 0x7fffffff;
             }
             // (a fixed odd-even transposition network keeps the arrays in registers; unused slots hold INT_MAX and stay behind)
 #pragma unroll
@@ -592,17 +570,17 @@ __device__ void emit_rows(int* s_out, int T, int* smem, int err, int n_edge_rows
             for (int k = 0; k < EMIT_SORT_MAX; ++k) {
                 if (k < n) {
                     const int j = w.v[k];
-                    col_idx[ebase + o + k] = j + cshift;
+                    dst.col_idx[ebase + o + k] = j + cshift;
                     // the value tree_to_adj wrote there (tree.py:184-192): 84 on the diagonal, deprel[j] for a child j, deprel[r] + 42 for the parent
-                    if (label) label[ebase + o + k] = j == r ? SELF_LOOP_ID : (pw_par(smem[j]) == r ? lab[j] : lab[r] + FWD_BOUND);
+                    if (dst.label) dst.label[ebase + o + k] = j == r ? SELF_LOOP_ID : (pw_par(L.pw[j]) == r ? L.lab[j] : L.lab[r] + FWD_BOUND);
                 }
-                if (k < nT && colT_idx) colT_idx[eTbase + oT + k] = w.vT[k] + cshift;
+                if (k < nT && dst.colT_idx) dst.colT_idx[eTbase + oT + k] = w.vT[k] + cshift;
                 if (k < 7) { hd[1 + k] = k < n ? w.v[k] + cshift : 0; hdT[1 + k] = k < nT ? w.vT[k] + cshift : 0; }
             }
-            int4* e = reinterpret_cast<int4*>(ell + (base + r) * 8);
+            int4* e = reinterpret_cast<int4*>(dst.ell + (base + r) * 8);
             e[0] = make_int4(hd[0], hd[1], hd[2], hd[3]); e[1] = make_int4(hd[4], hd[5], hd[6], hd[7]);
-            if (ellT) {
-                int4* eT = reinterpret_cast<int4*>(ellT + (base + r) * 8);
+            if (dst.ellT) {
+                int4* eT = reinterpret_cast<int4*>(dst.ellT + (base + r) * 8);
                 eT[0] = make_int4(hdT[0], hdT[1], hdT[2], hdT[3]); eT[1] = make_int4(hdT[4], hdT[5], hdT[6], hdT[7]);
             }
         };
@@ -619,11 +597,11 @@ __device__ void emit_rows(int* s_out, int T, int* smem, int err, int n_edge_rows
             }
         }
         __syncthreads();
-        const int nl = *n_long;
+        const int nl = *L.n_long;
         for (int x = wave; x < nl; x += PRUNE_THREADS / WAVE) {           // the few long rows: one wave each, scan form
-            const int me = einfo[longrows[x]];
-            const int r = me & 0xfff;
-            emit_row_scan(base, ebase, eTbase, cshift, lab, einfo, n_edge_rows, lane, me, lab[r], deg[r], degT[r], col_idx, label, colT_idx, ell, ellT);
+            const int me = L.einfo[L.longrows[x]];
+            const int r = er_token(me);
+            emit_row_scan(L, n_edge_rows, base, ebase, eTbase, cshift, me, L.lab[r], deg[r], degT[r], dst);
         }
         GCNPT_STAMP(stamps, 7);
         finish();
@@ -631,74 +609,68 @@ __device__ void emit_rows(int* s_out, int T, int* smem, int err, int n_edge_rows
     }
     if (packed && !resolve()) { finish(); return; }
     for (int q0 = 0; q0 < n_edge_rows; q0 += WAVE) {                  // rows, a chunk of 64 at a time (registers)
-        const int rw = q0 + lane < n_edge_rows ? einfo[q0 + lane] : 0;
-        const int rdeg = deg[rw & 0xfff], rdegT = degT[rw & 0xfff], rlab = lab[rw & 0xfff];
+        const int rw = q0 + lane < n_edge_rows ? L.einfo[q0 + lane] : 0;
+        const int rdeg = deg[er_token(rw)], rdegT = degT[er_token(rw)], rlab = L.lab[er_token(rw)];
         const int nq = min(WAVE, n_edge_rows - q0);
         for (int qq = wave; qq < nq; qq += PRUNE_THREADS / WAVE) {    // this wave's rows of the chunk
-            emit_row_scan(base, ebase, eTbase, cshift, lab, einfo, n_edge_rows, lane, __builtin_amdgcn_readlane(rw, qq), __builtin_amdgcn_readlane(rlab, qq),
-                          __builtin_amdgcn_readlane(rdeg, qq), __builtin_amdgcn_readlane(rdegT, qq), col_idx, label, colT_idx, ell, ellT);
+            emit_row_scan(L, n_edge_rows, base, ebase, eTbase, cshift, __builtin_amdgcn_readlane(rw, qq), __builtin_amdgcn_readlane(rlab, qq),
+                          __builtin_amdgcn_readlane(rdeg, qq), __builtin_amdgcn_readlane(rdegT, qq), dst);
         }
     }
     GCNPT_STAMP(stamps, 7);
     finish();
 }
 
-__global__ __launch_bounds__(PRUNE_THREADS) void prune_to_csr_kernel(
-    const int64_t* __restrict__ head, const int64_t* __restrict__ subj_pos, const int64_t* __restrict__ obj_pos,
-    const int64_t* __restrict__ deprel, const uint8_t* __restrict__ pad_mask, const int32_t* __restrict__ len_in,
-    int B, int T, int prune_k, int cap, int32_t* __restrict__ row_ptr, int32_t* __restrict__ col_idx,
-    int32_t* __restrict__ label, int32_t* __restrict__ rowT_ptr, int32_t* __restrict__ colT_idx,
-    int32_t* __restrict__ ell, int32_t* __restrict__ ellT, uint8_t* __restrict__ pool_mask,
-    int32_t* __restrict__ status, unsigned long long* stamps, const PackParams pk, int pk_dtype, int staged, const PackedOut po) {
-    extern __shared__ int smem[];  // carved in prune_sentence() (+ the entry lists of emit_rows when staged)
-    __shared__ int s_err;
+// in, len: the parse; dst: the arrays in either layout (PackedDst), sync: the look-back workspace of the packed one; pk, pk_dtype: the side job
+__global__ __launch_bounds__(PRUNE_THREADS) void prune_to_csr_kernel(const ParseSrc in, const int32_t* __restrict__ len,
+                                                                     int B, int T, int prune_k, int cap,
+                                                                     const PackedDst dst, unsigned long long* sync,
+                                                                     unsigned long long* stamps, const PackParams pk, int pk_dtype, int staged) {
+    extern __shared__ int smem[];
+    __shared__ PruneShared sh;
     if ((int)blockIdx.x >= B) {    // side job of gcnpt_prune_to_csr_pack: the launch leaves most CUs idle, these workgroups pack the weights
         pack_side_job(pk, pk_dtype, B);
         return;
     }
-
-    __shared__ int s_status, s_nrows, s_red[4], s_out[4], s_ticket;
+    const PruneLds L(smem, T);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // packed output: sentences in ticket order (PackedOut), else the workgroup's own
-    if (threadIdx.x == 0) s_ticket = po.cu ? (int)atomicAdd(po.sync + B, 1ull) : (int)blockIdx.x;
-    if (threadIdx.x == 0) { s_err = 0; s_status = 0; s_nrows = 0; s_red[0] = s_red[1] = s_red[2] = 0; s_red[3] = 0x7fffffff; }
+    // packed output: sentences in ticket order (see PK_VALID), else the workgroup's own
+    if (threadIdx.x == 0) sh.ticket = dst.cu ? (int)atomicAdd(sync + B, 1ull) : (int)blockIdx.x;
+    if (threadIdx.x == 0) { sh.err = 0; sh.status = 0; sh.nrows = 0; sh.red[0] = sh.red[1] = sh.red[2] = 0; sh.red[3] = 0x7fffffff; }
     GCNPT_STAMP_REAL(stamps);
     GCNPT_STAMP(stamps, 0);
-    __shared__ int s_maxlen;
-    if (threadIdx.x == 0) s_maxlen = 0;
+    if (threadIdx.x == 0) sh.maxlen = 0;
     __syncthreads();
-    const int b = s_ticket;
+    const int b = sh.ticket;
     const bool allw = T > PRUNE_WAVE0_T;
-    // status[B] = longest sentence of the batch (gcn.py:97): waves of workgroup 0 that have no token to prune count every sentence's
-    // non-pad slots while the others prune (wave 0 alone, or the waves holding the T tokens), so the launch needs neither a memset
-    // of that word nor one atomic per sentence.  (Big batches, or sentences that occupy every wave: atomicMax, see prune_impl.)
+    // the longest sentence (longest_by_atomic): waves of workgroup 0 that have no token to prune count every sentence's non-pad slots
+    // while the others prune (wave 0 alone, or the waves holding the T tokens), so the launch needs neither a memset of that word nor
+    // one atomic per sentence
+    const bool scan_longest = b == 0 && !longest_by_atomic(B, T);
     const int first_idle = allw ? (T + WAVE - 1) / WAVE : 1;
-    if (b == 0 && (long long)B * T <= PRUNE_SCAN_MAX && first_idle < PRUNE_THREADS / WAVE && wave >= first_idle) {
+    if (scan_longest && wave >= first_idle) {
         const int n_idle = PRUNE_THREADS / WAVE - first_idle;
         int m = 0;
         for (int sidx = wave - first_idle; sidx < B; sidx += n_idle) {
             int n;
-            if (pad_mask) {
+            if (in.pad_mask) {
                 n = 0;
                 for (int i0 = 0; i0 < T; i0 += WAVE) {
                     const int i = i0 + lane;
-                    n += __popcll(__ballot(i < T && pad_mask[(size_t)sidx * T + min(i, T - 1)] == 0));
+                    n += __popcll(__ballot(i < T && in.pad_mask[(size_t)sidx * T + min(i, T - 1)] == 0));
                 }
             } else {
-                n = min(max(len_in[sidx], 0), T);
+                n = min(max(len[sidx], 0), T);
             }
             m = max(m, n);
         }
-        if (lane == 0) atomicMax(&s_maxlen, m);
+        if (lane == 0) atomicMax(&sh.maxlen, m);
     }
-    if (allw) prune_sentence<true>(head, subj_pos, obj_pos, deprel, pad_mask, len_in, b, B, T, prune_k, cap, smem, &s_err, &s_status,
-                                   &s_nrows, s_red, row_ptr, rowT_ptr, ell, ellT, pool_mask, status, stamps, po, s_out);
-    else if (wave == 0) prune_sentence<false>(head, subj_pos, obj_pos, deprel, pad_mask, len_in, b, B, T, prune_k, cap, smem, &s_err, &s_status,
-                                              &s_nrows, s_red, row_ptr, rowT_ptr, ell, ellT, pool_mask, status, stamps, po, s_out);
+    if (allw) prune_sentence<true>(in, len, b, B, T, prune_k, cap, L, sh, dst, sync, stamps);
+    else if (wave == 0) prune_sentence<false>(in, len, b, B, T, prune_k, cap, L, sh, dst, sync, stamps);
     __syncthreads();
-    if (b == 0 && threadIdx.x == 0 && (long long)B * T <= PRUNE_SCAN_MAX && first_idle < PRUNE_THREADS / WAVE) status[B] = s_maxlen;
-    const PackedEmit pe{po, b, B, row_ptr, rowT_ptr, status, pool_mask, s_red, &s_status};
-    emit_rows(s_out, T, smem, s_status, s_nrows, lane, wave, staged != 0, col_idx, label, colT_idx, ell, ellT, stamps, pe);
+    if (scan_longest && threadIdx.x == 0) dst.sent_status[B] = sh.maxlen;
+    emit_rows(L, sh, b, B, T, staged != 0, dst, sync, stamps);
     // (packed output that did not fit: the per-sentence code stays what the pruning found; the batch-level status says E_CAPACITY)
 }
 
@@ -792,35 +764,36 @@ __global__ void csr_to_adj_kernel(const int32_t* __restrict__ row_ptr, const int
 
 using namespace gcnpt;
 
-static int prune_impl(void* stream, const int64_t* head, const int64_t* subj_pos, const int64_t* obj_pos,
-                      const int64_t* deprel, const uint8_t* pad_mask, const int32_t* len, int B, int T,
-                      int prune_k, int cap, int32_t* row_ptr, int32_t* col_idx, int32_t* label,
-                      int32_t* rowT_ptr, int32_t* colT_idx, int32_t* ell, int32_t* ellT, uint8_t* pool_mask,
-                      int32_t* status, const SideJob& sj, const PackedOut& po = PackedOut{}) {
-    GCNPT_REQUIRE(head && subj_pos && obj_pos && deprel && (pad_mask || len), "prune_to_csr: null input pointer");
-    GCNPT_REQUIRE(row_ptr && col_idx && ell && status, "prune_to_csr: null output pointer");
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (ellT == nullptr), "prune_to_csr: rowT_ptr, colT_idx and ellT go together");
+// the padded layout as the pruner's destination: no cu, the mask and the status in the padded layout's two members
+static PackedDst padded_dst(const TreeArrays& a) {
+    PackedDst d{};
+    d.row_ptr = a.row_ptr; d.col_idx = a.col_idx; d.label = a.label; d.rowT_ptr = a.rowT_ptr; d.colT_idx = a.colT_idx;
+    d.ell = a.ell; d.ellT = a.ellT; d.pool_mask_padded = a.pool_mask; d.sent_status = a.status;
+    return d;
+}
+
+// dst.cu == NULL: the padded layout, cap entries per sentence (sync unused)
+static int prune_impl(void* stream, const ParseSrc& in, const int32_t* len, int B, int T, int prune_k, int cap, const PackedDst& dst, uint64_t* sync,
+                      const SideJob& sj) {
+    GCNPT_REQUIRE(in.head && in.subj_pos && in.obj_pos && in.deprel && (in.pad_mask || len), "prune_to_csr: null input pointer");
+    GCNPT_REQUIRE(dst.row_ptr && dst.col_idx && dst.ell && dst.sent_status, "prune_to_csr: null output pointer");
+    const int rc = check_transposed("prune_to_csr", dst.rowT_ptr, dst.colT_idx, dst.ellT);
+    if (rc != GCNPT_OK) return rc;
     GCNPT_REQUIRE(B > 0 && T > 0 && cap > 0, "prune_to_csr: B, T, cap must be positive (B=%d T=%d cap=%d)", B, T, cap);
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr), "prune_to_csr: rowT_ptr and colT_idx go together");
     if (prune_k < 0)
         return fail(GCNPT_E_PRUNE_NEGATIVE, "prune_k=%d: the reference fork only works with prune_k >= 0 "
                     "(model/tree.py:194 reads Tree.head, which the unpruned branch never sets)", prune_k);
     if ((long long)B * cap > 0x7fffffffLL) return fail(GCNPT_E_UNSUPPORTED, "prune_to_csr: B*cap overflows int32");
-    // 7 words per token for the pruning phases; + 7 more for the staged row emission (3T forward + 3T transposed entries, T for the
-    // long-row list) when that still fits LDS (T <= ~2800)
-    const size_t lds_base = sizeof(int) * ((size_t)7 * T + 4), lds_staged = sizeof(int) * ((size_t)14 * T + 4);
-    const int staged = lds_staged <= 160 * 1024 - 256 ? 1 : 0;
-    const size_t lds = staged ? lds_staged : lds_base;
+    // the staged row emission when its entry lists still fit LDS (T <= ~2900)
+    const int staged = PruneLds::bytes(T, true) <= 160 * 1024 - 256 ? 1 : 0;
+    const size_t lds = PruneLds::bytes(T, staged);
     if (T > PRUNE_MAX_T) return fail(GCNPT_E_UNSUPPORTED, "prune_to_csr: T=%d exceeds the %d tokens a sentence may have", T, PRUNE_MAX_T);
     hipStream_t s = (hipStream_t)stream;
-    // sentences beyond ~2300 tokens need more than the default 64 KB of LDS (7 words per token); minus the kernel's few static words
+    // sentences beyond ~2300 tokens need more than the default 64 KB of LDS; minus the kernel's few static words
     if (lds > 64 * 1024) GCNPT_LDS_ATTR_ONCE(prune_to_csr_kernel, 160 * 1024 - 256);
-    // big batches, and sentences that occupy every wave of their workgroup: atomicMax per sentence (see the kernel)
-    if ((long long)B * T > PRUNE_SCAN_MAX || (T > PRUNE_WAVE0_T && T + WAVE > PRUNE_THREADS))
-        GCNPT_HIP_CHECK(hipMemsetAsync(status + B, 0, sizeof(int32_t), s));
-    hipLaunchKernelGGL(prune_to_csr_kernel, dim3(B + sj.blocks), dim3(PRUNE_THREADS), lds, s, head, subj_pos, obj_pos, deprel,
-                       pad_mask, len, B, T, prune_k, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status,
-                       static_cast<unsigned long long*>(g_debug_stamps), sj.pk, sj.dtype, staged, po);
+    if (longest_by_atomic(B, T)) GCNPT_HIP_CHECK(hipMemsetAsync(dst.sent_status + B, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(prune_to_csr_kernel, dim3(B + sj.blocks), dim3(PRUNE_THREADS), lds, s, in, len, B, T, prune_k, cap, dst,
+                       reinterpret_cast<unsigned long long*>(sync), static_cast<unsigned long long*>(g_debug_stamps), sj.pk, sj.dtype, staged);
     GCNPT_HIP_CHECK(hipGetLastError());
     return GCNPT_OK;
 }
@@ -830,8 +803,8 @@ extern "C" int gcnpt_prune_to_csr(void* stream, const int64_t* head, const int64
                                   int prune_k, int cap, int32_t* row_ptr, int32_t* col_idx, int32_t* label,
                                   int32_t* rowT_ptr, int32_t* colT_idx, int32_t* ell, int32_t* ellT, uint8_t* pool_mask,
                                   int32_t* status) {
-    return prune_impl(stream, head, subj_pos, obj_pos, deprel, pad_mask, len, B, T, prune_k, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx,
-                      ell, ellT, pool_mask, status, SideJob{});
+    const TreeArrays out{row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status};
+    return prune_impl(stream, ParseSrc{head, subj_pos, obj_pos, deprel, pad_mask}, len, B, T, prune_k, cap, padded_dst(out), nullptr, SideJob{});
 }
 
 extern "C" int gcnpt_prune_to_csr_pack(void* stream, const int64_t* head, const int64_t* subj_pos, const int64_t* obj_pos,
@@ -843,8 +816,8 @@ extern "C" int gcnpt_prune_to_csr_pack(void* stream, const int64_t* head, const 
     SideJob sj;
     const int rc = side_job(sj, false, PRUNE_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
     if (rc != GCNPT_OK) return rc;
-    return prune_impl(stream, head, subj_pos, obj_pos, deprel, pad_mask, len, B, T, prune_k, cap, row_ptr, col_idx, label, rowT_ptr, colT_idx,
-                      ell, ellT, pool_mask, status, sj);
+    const TreeArrays out{row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, status};
+    return prune_impl(stream, ParseSrc{head, subj_pos, obj_pos, deprel, pad_mask}, len, B, T, prune_k, cap, padded_dst(out), nullptr, sj);
 }
 
 // The pruner writing the token-packed layout itself (what gcnpt_pack_trees makes of gcnpt_prune_to_csr's arrays, bit for bit), optionally
@@ -862,18 +835,18 @@ extern "C" int gcnpt_prune_to_csr_packed(void* stream, const int64_t* head, cons
     SideJob sj;
     const int rc = side_job(sj, true, PRUNE_THREADS, n_layers, W, H, Din, dtype, w_fwd, w_bwd);
     if (rc != GCNPT_OK) return rc;
-    PackedOut po{cu_seqlens, row_sent, pool_mask_padded, reinterpret_cast<unsigned long long*>(sync_ws), status, n_rows, nnz_cap};
-    return prune_impl(stream, head, subj_pos, obj_pos, deprel, pad_mask, len, B, T, prune_k, 3 * T, row_ptr, col_idx, label, rowT_ptr, colT_idx,
-                      ell, ellT, pool_mask, sent_status, sj, po);
+    const PackedDst dst{cu_seqlens, row_ptr, col_idx, label, rowT_ptr, colT_idx, ell, ellT, pool_mask, row_sent, status, n_rows, nnz_cap,
+                        pool_mask_padded, sent_status};
+    return prune_impl(stream, ParseSrc{head, subj_pos, obj_pos, deprel, pad_mask}, len, B, T, prune_k, 3 * T, dst, sync_ws, sj);
 }
 
 extern "C" int gcnpt_adj_to_csr(void* stream, const float* adj, int B, int T, int cap, int32_t* row_ptr,
                                 int32_t* col_idx, int32_t* label, int32_t* rowT_ptr, int32_t* colT_idx, int32_t* ell,
                                 int32_t* ellT, uint8_t* pool_mask, int32_t* status) {
     GCNPT_REQUIRE(adj && row_ptr && col_idx && ell && status, "adj_to_csr: null pointer");
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (ellT == nullptr), "adj_to_csr: rowT_ptr, colT_idx and ellT go together");
+    const int rc = check_transposed("adj_to_csr", rowT_ptr, colT_idx, ellT);
+    if (rc != GCNPT_OK) return rc;
     GCNPT_REQUIRE(B > 0 && T > 0 && cap > 0, "adj_to_csr: B, T, cap must be positive");
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr), "adj_to_csr: rowT_ptr and colT_idx go together");
     if ((long long)B * cap > 0x7fffffffLL) return fail(GCNPT_E_UNSUPPORTED, "adj_to_csr: B*cap overflows int32");
     const size_t lds = sizeof(int) * ((size_t)2 * T + 2 + ADJ_THREADS);
     if (lds > 150 * 1024) return fail(GCNPT_E_UNSUPPORTED, "adj_to_csr: T=%d needs %zu B of LDS", T, lds);

@@ -1,7 +1,8 @@
-// The two layouts of a batch's tree arrays (include/gcnpt.h) as the rewrite kernels of tree_rewrite_kernels.hip see them, and the ONE
-// copy of each rule they share: how a source sentence becomes a sentence of the token-packed layout, how an ELL head is shifted, how a
-// cached sentence is looked up, and the workgroup reduction behind their offsets.  Whichever producer wrote a layout, the arrays are the
-// same bit for bit (tests/test_gpu_packed.py, tests/test_gpu_parity.py).
+// The two layouts of a batch's tree arrays (include/gcnpt.h) as the pruner (tree_kernels.hip) and the rewrite kernels of
+// tree_rewrite_kernels.hip see them, and the ONE copy of each rule they share: the header of a packed sentence, how a source sentence
+// becomes a sentence of the token-packed layout, how an ELL head is shifted or left empty, how a cached sentence is looked up, the
+// workgroup reduction behind their offsets, and the host check that the transposed arrays come together.  Whichever producer wrote a
+// layout, the arrays are the same bit for bit (tests/test_gpu_packed.py, tests/test_gpu_parity.py).
 #pragma once
 #include "gcnpt_common.h"
 
@@ -22,8 +23,11 @@ struct TreeArrays {
     uint8_t* pool_mask;
     int32_t* status;
 };
-// a token-packed batch that a rewrite writes: only through write_packed_sentence(), but for the two arrays of the PADDED layout that
-// come with it when a cache is the source (NULL otherwise), which gather_trees_packed_kernel fills itself
+// a token-packed batch.  The rewrites write it only through write_packed_sentence(), but for the two arrays of the PADDED layout that
+// come with it when a cache or the parse is the source (NULL otherwise), which gather_trees_packed_kernel fills itself.  The pruner
+// writes every member itself (tree_kernels.hip: emit_rows), the header through write_packed_header(); it is also its destination for
+// the padded layout: cu == NULL, the arrays a TreeArrays' with pool_mask_padded as its mask and sent_status as its status, the members
+// of the packed layout alone unused.
 struct PackedDst {
     int32_t *cu, *row_ptr, *col_idx, *label, *rowT_ptr, *colT_idx, *ell, *ellT;
     uint8_t* pool_mask;
@@ -64,6 +68,20 @@ __device__ __forceinline__ void block_reduce(int (&v)[N], int (*scratch)[N]) {
         for (int q = 0; q < N; ++q) v[q] = join(q, v[q], scratch[w][q]);
 }
 
+// rowT_ptr, colT_idx and ellT of a destination: all three or none (host; what: the entry point, for the message)
+inline int check_transposed(const char* what, const void* rowT_ptr, const void* colT_idx, const void* ellT) {
+    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr) && (rowT_ptr == nullptr) == (ellT == nullptr),
+                  "%s: rowT_ptr, colT_idx and ellT go together", what);
+    return GCNPT_OK;
+}
+
+// The ELL head of a row without entries, in both patterns (ellT: NULL or the transposed heads): count 0, zeros in the slots.
+__device__ __forceinline__ void zero_ell_head(size_t row, int32_t* ell, int32_t* ellT) {
+    const i32x4_t z = {0, 0, 0, 0};
+    reinterpret_cast<i32x4_t*>(ell + row * 8)[0] = z; reinterpret_cast<i32x4_t*>(ell + row * 8)[1] = z;
+    if (ellT) { reinterpret_cast<i32x4_t*>(ellT + row * 8)[0] = z; reinterpret_cast<i32x4_t*>(ellT + row * 8)[1] = z; }
+}
+
 // One 16-byte half of a row's ELL head ([count, c0..c2] / [c3..c6]) into the packed layout: cu added to the live slots, zeros in the
 // others.  head_src / head_dst: the row's 8 words; !ok: an all-zero head, nothing is read.
 __device__ __forceinline__ void shift_ell_half(const int32_t* head_src, int32_t* head_dst, int half, bool ok, int cu) {
@@ -77,28 +95,36 @@ __device__ __forceinline__ void shift_ell_half(const int32_t* head_src, int32_t*
     reinterpret_cast<i32x4_t*>(head_dst)[half] = v;
 }
 
+// The header of sentence b of a token-packed batch (len rows from cu, nnz / nnzT entries from eo / eoT), by thread 0; every thread gets
+// whether the sentence fits the n_rows rows and nnz_cap entries of the destination, of which these are the cu, row_ptr, rowT_ptr and
+// status: one that does not writes nothing but cu[b].  The last sentence writes the batch's totals and closing offsets: offsets grow
+// with b, so it fits iff every sentence does.  (Values and pointers, not the PackedDst: see lookup_cached_sentence.)
+__device__ __forceinline__ bool write_packed_header(int b, int B, int cu, int eo, int eoT, int len, int nnz, int nnzT, int32_t* cu_out,
+                                                    int32_t* row_ptr, int32_t* rowT_ptr, int32_t* status, int n_rows, int nnz_cap) {
+    const bool fits = cu + len <= n_rows && eo + nnz <= nnz_cap && eoT + nnzT <= nnz_cap;
+    if (threadIdx.x == 0) {
+        cu_out[b] = cu;
+        if (b == B - 1) {
+            cu_out[B] = cu + len;
+            status[0] = fits ? 0 : GCNPT_E_CAPACITY;
+            status[1] = cu + len;
+            if (fits) {
+                row_ptr[cu + len] = eo + nnz;
+                if (rowT_ptr) rowT_ptr[cu + len] = eoT + nnzT;
+            }
+        }
+    }
+    return fits;
+}
+
 // Sentence b of a token-packed batch (layout: gcnpt_pack_trees in include/gcnpt.h), by all THREADS of a workgroup: rows from cu,
-// entries from eo / eoT (the sums of len, nnz, nnzT over the sentences before it); columns and live ELL slots shifted by cu.  A
-// sentence that does not fit n_rows / nnz_cap writes nothing but cu[b].  The last sentence writes the batch's totals: offsets grow
-// with b, so it fits iff every sentence does.
+// entries from eo / eoT (the sums of len, nnz, nnzT over the sentences before it); columns and live ELL slots shifted by cu.
 template <int THREADS>
 __device__ __forceinline__ void write_packed_sentence(const TreeSrc& src, const SentenceSrc& s, int b, int B, int cu, int eo, int eoT,
                                                       const PackedDst& dst) {
     const int t = threadIdx.x;
-    const bool fits = cu + s.len <= dst.n_rows && eo + s.nnz <= dst.nnz_cap && eoT + s.nnzT <= dst.nnz_cap;
-    if (t == 0) {
-        dst.cu[b] = cu;
-        if (b == B - 1) {
-            dst.cu[B] = cu + s.len;
-            dst.status[0] = fits ? 0 : GCNPT_E_CAPACITY;
-            dst.status[1] = cu + s.len;
-            if (fits) {
-                dst.row_ptr[cu + s.len] = eo + s.nnz;
-                if (dst.rowT_ptr) dst.rowT_ptr[cu + s.len] = eoT + s.nnzT;
-            }
-        }
-    }
-    if (!fits) return;
+    if (!write_packed_header(b, B, cu, eo, eoT, s.len, s.nnz, s.nnzT, dst.cu, dst.row_ptr, dst.rowT_ptr, dst.status, dst.n_rows, dst.nnz_cap))
+        return;
     for (int i = t; i < s.len; i += THREADS) {
         dst.row_ptr[cu + i] = eo + (s.ok ? src.row_ptr[s.row + i] - s.rp0 : 0);
         if (dst.rowT_ptr) dst.rowT_ptr[cu + i] = eoT + (s.ok ? src.rowT_ptr[s.row + i] - s.rpT0 : 0);

@@ -151,12 +151,7 @@ __global__ __launch_bounds__(REWRITE_THREADS) void compact_trees_kernel(const Tr
         if (j < Tc) {
             tok[(size_t)b * Tc + j] = -1;
             dst.pool_mask[(size_t)b * Tc + j] = 1;
-            int4* e = reinterpret_cast<int4*>(dst.ell + ((size_t)b * Tc + j) * 8);
-            e[0] = make_int4(0, 0, 0, 0); e[1] = make_int4(0, 0, 0, 0);
-            if (dst.ellT) {
-                int4* eT = reinterpret_cast<int4*>(dst.ellT + ((size_t)b * Tc + j) * 8);
-                eT[0] = make_int4(0, 0, 0, 0); eT[1] = make_int4(0, 0, 0, 0);
-            }
+            zero_ell_head((size_t)b * Tc + j, dst.ell, dst.ellT);
         }
     }
     if (!ok) return;
@@ -224,8 +219,8 @@ int check_request(const char* what, const int32_t* src_label, const int32_t* src
                   const int32_t* src_ellT, const uint8_t* src_pool_mask, const int32_t* label, const int32_t* rowT_ptr,
                   const int32_t* colT_idx, const int32_t* ellT, const uint8_t* pool_mask) {
     GCNPT_REQUIRE(!label || src_label, "%s: labels wanted but the source holds none", what);
-    GCNPT_REQUIRE((rowT_ptr == nullptr) == (colT_idx == nullptr) && (rowT_ptr == nullptr) == (ellT == nullptr),
-                  "%s: rowT_ptr, colT_idx and ellT go together", what);
+    const int rc = check_transposed(what, rowT_ptr, colT_idx, ellT);
+    if (rc != GCNPT_OK) return rc;
     GCNPT_REQUIRE(!rowT_ptr || (src_rowT_ptr && src_colT_idx && src_ellT), "%s: transposed pattern wanted but the source holds none", what);
     GCNPT_REQUIRE(!pool_mask || src_pool_mask, "%s: pool mask wanted but the source holds none", what);
     return GCNPT_OK;

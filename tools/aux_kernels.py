@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Runs the auxiliary kernels (pool3, diagonal_deprel layer, the four tree-array rewrites) at the bench shape a few hundred times, for
-`rocprofv3 --kernel-trace --stats` (developer tool: their durations are not part of the headline step)."""
+"""Runs the auxiliary kernels (pool3, diagonal_deprel layer, the four tree-array rewrites) at the bench shape a few hundred times, and
+the pruner in both layouts at three shapes, for `rocprofv3 --kernel-trace --stats` (developer tool: their durations are not part of
+the headline step)."""
 import os
 import sys
 
@@ -40,6 +41,14 @@ def main():
         trees.pack(lens)
         cache.batch_packed(idx, T, n_rows=n_rows)
         trees.compact(Tc=Tc)
+    # the pruner, padded and token-packed: all-waves form, wave-0 form, a shard of 16 long sentences
+    for Bp, Tp, K in ((50, 100, 1), (50, 50, 1), (16, 300, 2)):
+        tp = synthetic.random_tree_batch(2, Bp, Tp, "tacred")
+        args = [t(tp[k]) for k in ("head", "subj_pos", "obj_pos", "deprel")]
+        lens_dev, lens_host = t(tp["lens"]), tp["lens"].tolist()
+        for _ in range(100):
+            tree.prune_to_csr(*args, K, lens=lens_dev)
+            tree.prune_to_csr_packed(*args, K, lens_host, n_rows=int(sum(lens_host)))
     torch.cuda.synchronize()
     print("done")
 
