@@ -14,6 +14,11 @@
 //   dE[deprel[c]] += uf[c] * h[c]   dE[deprel[c]+42] += ur[c] * h[c]   (fp32 atomics, only tokens that have such edges)
 //   dE[84] += sum_c dz[c] * h[c]    (its own column-reduction launch: 64 atomics per element instead of one per workgroup)
 // adj[r,c] for r in column c's transposed list is looked up in row r's (short) CSR segment.
+//
+// Both layouts run the same three kernels (PACKED is a template parameter, as in pool_kernels.hip; row addressing: RowAddr in
+// layer_common.h).  Token-packed (gcnpt_diag_layer_*_packed, PackedTrees): h, out, Y, dY, dh are [n_rows,H], deprel is a packed int64
+// [n_rows] array, row_ptr / rowT_ptr have n_rows + 1 entries and the columns are packed rows.  Rows from *n_live = cu_seqlens[B] on
+// belong to no sentence and nobody wrote their row_ptr / rowT_ptr: they read no adjacency, get zero rows of out / dh and add nothing to dE.
 #include "layer_common.h"
 
 namespace gcnpt {
@@ -33,9 +38,10 @@ struct DiagParams {
     const float* E;           // [85,H]
     const int64_t* deprel;    // [N]
     const int32_t *row_ptr, *col_idx, *label, *rowT_ptr, *colT_idx;
+    const int32_t* n_live;    // packed: device word holding cu_seqlens[B]; rows from there on are dead
     void* out;                // fwd: [N,H]      bwd: dh [N,H]
     float* dE;                // bwd: [85,H], accumulated
-    int N, T, H;
+    int N, T, H, nnz_cap;     // nnz_cap: packed, entries allocated
     float scale;
     unsigned drop_thresh16;
     uint64_t seed;
@@ -51,9 +57,9 @@ __device__ __forceinline__ int diag_emb_row(int lab, int rel) {
 }
 __device__ __forceinline__ int diag_rel(const int64_t* deprel, int i) { return (int)max((int64_t)0, min(deprel[i], (int64_t)(DG_NE - 1))); }
 
-template <typename T, int CPL>
+template <typename T, int CPL, bool PACKED>
 __global__ __launch_bounds__(DG_THREADS) void diag_fwd_kernel(const DiagParams p) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // (provably wave-uniform: the row's index chain is scalar)
     const T* h = static_cast<const T*>(p.h);
     T* out = static_cast<T*>(p.out);
     const int H = p.H;
@@ -61,8 +67,13 @@ __global__ __launch_bounds__(DG_THREADS) void diag_fwd_kernel(const DiagParams p
     for (int rr = wave; rr < DG_ROWS; rr += DG_WAVES) {
         const int r = blockIdx.x * DG_ROWS + rr;
         if (r >= p.N) break;
-        const int b = r / p.T, t = r - b * p.T;
-        const int beg = p.row_ptr[b * (p.T + 1) + t], end = p.row_ptr[b * (p.T + 1) + t + 1];
+        const RowAddr a = row_addr<PACKED>(p.n_live, r, p.T);
+        if (PACKED && !a.live) {                                                        // wave-uniform
+            zero_row<T, CPL>(out + (size_t)r * H, H, lane);
+            continue;
+        }
+        int beg, end;
+        row_seg<PACKED>(p.row_ptr, a, a.t, p.nnz_cap, beg, end);
         const float den = (float)(end - beg + 1);                                       // gcn.py:138 + 390
         for (int c0 = lane * CPL; c0 < round_up(H, 64 * CPL); c0 += 64 * CPL) {
             const int cc = min(c0, H - CPL), live = c0 < H;
@@ -72,10 +83,11 @@ __global__ __launch_bounds__(DG_THREADS) void diag_fwd_kernel(const DiagParams p
 #pragma unroll
             for (int j = 0; j < CPL; ++j) acc[j] = ev[j] * hv[j];                      // gcn.py:289-294
             for (int e = beg; e < end; ++e) {
-                const int c = p.col_idx[e];
-                const int id = diag_emb_row(p.label[e], diag_rel(p.deprel, b * p.T + c));
+                const int c = a.col0 + p.col_idx[e];
+                if (PACKED && (unsigned)c >= (unsigned)p.N) continue;                   // (memory safety under a failed pack, as row_seg's clamp)
+                const int id = diag_emb_row(p.label[e], diag_rel(p.deprel, c));
                 if (id < 0) continue;                                                   // wave-uniform
-                dgio<T, CPL>::ld(h + ((size_t)b * p.T + c) * H + cc, live, hv);
+                dgio<T, CPL>::ld(h + (size_t)c * H + cc, live, hv);
                 dgio<float, CPL>::ld(p.E + (size_t)id * H + cc, live, ev);
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) acc[j] = __builtin_fmaf(ev[j], hv[j], acc[j]);
@@ -95,9 +107,9 @@ __global__ __launch_bounds__(DG_THREADS) void diag_fwd_kernel(const DiagParams p
     }
 }
 
-template <typename T, int CPL>
+template <typename T, int CPL, bool PACKED>
 __global__ __launch_bounds__(DG_THREADS) void diag_bwd_kernel(const DiagParams p) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const T* h = static_cast<const T*>(p.h);
     const T* Y = static_cast<const T*>(p.y);
     const T* dY = static_cast<const T*>(p.dy);
@@ -110,29 +122,40 @@ __global__ __launch_bounds__(DG_THREADS) void diag_bwd_kernel(const DiagParams p
         for (int rr = wave; rr < DG_ROWS; rr += DG_WAVES) {
             const int c = blockIdx.x * DG_ROWS + rr;                                      // this wave's token (a COLUMN of adj)
             if (c >= p.N) break;
-            const int b = c / p.T, t = c - b * p.T;
-            const int rp = b * (p.T + 1);
-            const int rel = diag_rel(p.deprel, c);
+            const RowAddr a = row_addr<PACKED>(p.n_live, c, p.T);
             float uf[CPL], ur[CPL], dz[CPL], yv[CPL], gv[CPL], hv[CPL], out[CPL];
+            if (PACKED && !a.live) {                                                      // wave-uniform
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) out[j] = 0.0f;
+                if (live) dgio<T, CPL>::st(dh + (size_t)c * H + cc, live, out);
+                continue;
+            }
+            const int rel = diag_rel(p.deprel, c);
             bool any_f = false, any_r = false;
 #pragma unroll
             for (int j = 0; j < CPL; ++j) uf[j] = ur[j] = 0.0f;
             {                                                                             // own dz
-                const float s = p.scale / (float)(p.row_ptr[rp + t + 1] - p.row_ptr[rp + t] + 1);
+                int ob, oe;
+                row_seg<PACKED>(p.row_ptr, a, a.t, p.nnz_cap, ob, oe);
+                const float s = p.scale / (float)(oe - ob + 1);
                 dgio<T, CPL>::ld(Y + (size_t)c * H + cc, live, yv);
                 dgio<T, CPL>::ld(dY + (size_t)c * H + cc, live, gv);
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) dz[j] = yv[j] > 0.0f ? gv[j] * s : 0.0f;
             }
-            for (int e = p.rowT_ptr[rp + t]; e < p.rowT_ptr[rp + t + 1]; ++e) {
+            int tb, te;
+            row_seg<PACKED>(p.rowT_ptr, a, a.t, p.nnz_cap, tb, te);
+            for (int e = tb; e < te; ++e) {
                 const int tr = p.colT_idx[e];                                             // adj[b, tr, t] != 0
-                const int rb = p.row_ptr[rp + tr], re = p.row_ptr[rp + tr + 1];
+                if (PACKED && (unsigned)tr >= (unsigned)p.N) continue;                    // (memory safety under a failed pack)
+                int rb, re;
+                row_seg<PACKED>(p.row_ptr, a, tr, p.nnz_cap, rb, re);
                 int lab = 0;
-                for (int q = rb; q < re; ++q) lab = p.col_idx[q] == t ? p.label[q] : lab;
+                for (int q = rb; q < re; ++q) lab = p.col_idx[q] == a.t ? p.label[q] : lab;
                 const int id = diag_emb_row(lab, rel);
                 if (id < 0) continue;                                                     // wave-uniform
                 const float s = p.scale / (float)(re - rb + 1);
-                const size_t r = (size_t)b * p.T + tr;
+                const size_t r = (size_t)(a.col0 + tr);
                 dgio<T, CPL>::ld(Y + r * H + cc, live, yv);
                 dgio<T, CPL>::ld(dY + r * H + cc, live, gv);
                 if (lab < DG_FWD) {
@@ -175,7 +198,7 @@ __global__ __launch_bounds__(DG_THREADS) void diag_bwd_kernel(const DiagParams p
 
 // dE[84] += sum_c dz[c] * h[c]: a column reduction over all N rows on its own, so that one element of that row receives
 // DG_SELF_BLOCKS float atomics instead of one per workgroup of the kernel above (same-address atomics serialise)
-template <typename T, int CPL>
+template <typename T, int CPL, bool PACKED>
 __global__ __launch_bounds__(DG_SELF_WAVES * 64) void diag_selfgrad_kernel(const DiagParams p) {
     __shared__ float red[DG_SELF_WAVES][64 * CPL];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -183,8 +206,9 @@ __global__ __launch_bounds__(DG_SELF_WAVES * 64) void diag_selfgrad_kernel(const
     const T* Y = static_cast<const T*>(p.y);
     const T* dY = static_cast<const T*>(p.dy);
     const int H = p.H;
-    const int per = ceil_div(p.N, (int)gridDim.x);
-    const int r_lo = blockIdx.x * per, r_hi = min(p.N, r_lo + per);
+    const int n = PACKED ? min(max(*p.n_live, 0), p.N) : p.N;               // packed: the live rows (dead ones hold no token)
+    const int per = ceil_div(n, (int)gridDim.x);
+    const int r_lo = blockIdx.x * per, r_hi = min(n, r_lo + per);
     const int c0 = (blockIdx.y * 64 + lane) * CPL;
     const int cc = min(c0, H - CPL), live = c0 < H;
     float acc[CPL];
@@ -196,11 +220,13 @@ __global__ __launch_bounds__(DG_SELF_WAVES * 64) void diag_selfgrad_kernel(const
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const int r = min(r0 + u * DG_SELF_WAVES, r_hi - 1);
-            const int b = r / p.T, t = r - b * p.T;
+            const RowAddr a = row_addr<PACKED>(p.n_live, r, p.T);
+            int ob, oe;
+            row_seg<PACKED>(p.row_ptr, a, a.t, p.nnz_cap, ob, oe);
             dgio<T, CPL>::ld(Y + (size_t)r * H + cc, live, yv[u]);
             dgio<T, CPL>::ld(dY + (size_t)r * H + cc, live, gv[u]);
             dgio<T, CPL>::ld(h + (size_t)r * H + cc, live, hv[u]);
-            s[u] = p.scale / (float)(p.row_ptr[b * (p.T + 1) + t + 1] - p.row_ptr[b * (p.T + 1) + t] + 1);
+            s[u] = p.scale / (float)(oe - ob + 1);
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
@@ -223,15 +249,15 @@ __global__ __launch_bounds__(DG_SELF_WAVES * 64) void diag_selfgrad_kernel(const
     }
 }
 
-template <bool BWD>
+template <bool BWD, bool PACKED>
 static int launch_diag(hipStream_t s, const DiagParams& p, int dtype, bool vec) {
     const dim3 grid(ceil_div(p.N, DG_ROWS)), block(DG_THREADS);
 #define GCNPT_DIAG_LAUNCH(T, CPL)                                                             \
     do {                                                                                      \
         if (BWD) {                                                                            \
-            hipLaunchKernelGGL((diag_bwd_kernel<T, CPL>), grid, block, 0, s, p);              \
-            hipLaunchKernelGGL((diag_selfgrad_kernel<T, CPL>), dim3(std::min(DG_SELF_BLOCKS, p.N), ceil_div(p.H, 64 * CPL)), dim3(DG_SELF_WAVES * 64), 0, s, p); \
-        } else hipLaunchKernelGGL((diag_fwd_kernel<T, CPL>), grid, block, 0, s, p);           \
+            hipLaunchKernelGGL((diag_bwd_kernel<T, CPL, PACKED>), grid, block, 0, s, p);              \
+            hipLaunchKernelGGL((diag_selfgrad_kernel<T, CPL, PACKED>), dim3(std::min(DG_SELF_BLOCKS, p.N), ceil_div(p.H, 64 * CPL)), dim3(DG_SELF_WAVES * 64), 0, s, p); \
+        } else hipLaunchKernelGGL((diag_fwd_kernel<T, CPL, PACKED>), grid, block, 0, s, p);           \
     } while (0)
     if (dtype == GCNPT_F32) {
         if (vec) GCNPT_DIAG_LAUNCH(float, 4); else GCNPT_DIAG_LAUNCH(float, 1);
@@ -247,34 +273,70 @@ static int launch_diag(hipStream_t s, const DiagParams& p, int dtype, bool vec) 
 
 using namespace gcnpt;
 
-extern "C" int gcnpt_diag_layer_fwd(void* stream, const void* h, int dtype, const float* E, const int64_t* deprel,
-                                    const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label, int B, int T, int H,
-                                    void* out, float drop_p, uint64_t seed, const uint64_t* seed_dev) {
-    GCNPT_REQUIRE(h && E && deprel && row_ptr && col_idx && label && out, "diag_layer_fwd: null pointer");
-    GCNPT_REQUIRE(B > 0 && T > 0 && H > 0 && dtype_ok(dtype), "diag_layer_fwd: bad argument");
-    GCNPT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f, "diag_layer_fwd: drop_p must be in [0,1)");
-    if ((long long)B * T > 0x7fffffffLL / 2) return fail(GCNPT_E_UNSUPPORTED, "diag_layer_fwd: B*T too large");
+// Both layouts through one wrapper per direction.  n_live == nullptr: the padded entry points (n_rows = B*T); else the packed ones.
+static int diag_fwd(void* stream, const void* h, int dtype, const float* E, const int64_t* deprel, const int32_t* row_ptr,
+                    const int32_t* col_idx, const int32_t* label, const int32_t* n_live, bool packed, long long n_rows, int T, int nnz_cap, int H,
+                    void* out, float drop_p, uint64_t seed, const uint64_t* seed_dev, const char* what) {
+    GCNPT_REQUIRE(h && E && deprel && row_ptr && col_idx && label && out && (!packed || n_live), "%s: null pointer", what);
+    GCNPT_REQUIRE(n_rows > 0 && T > 0 && H > 0 && dtype_ok(dtype) && (!packed || nnz_cap > 0), "%s: bad argument", what);
+    GCNPT_REQUIRE(drop_p >= 0.0f && drop_p < 1.0f, "%s: drop_p must be in [0,1)", what);
+    if (n_rows > 0x7fffffffLL / 2) return fail(GCNPT_E_UNSUPPORTED, "%s: too many rows", what);
     DiagParams p{};
     p.h = h; p.E = E; p.deprel = deprel; p.row_ptr = row_ptr; p.col_idx = col_idx; p.label = label; p.out = out;
-    p.N = B * T; p.T = T; p.H = H;
+    p.n_live = n_live; p.nnz_cap = nnz_cap;
+    p.N = (int)n_rows; p.T = T; p.H = H;
     p.scale = drop_p > 0.0f ? 1.0f / (1.0f - drop_p) : 1.0f;
     p.drop_thresh16 = (unsigned)((double)drop_p * 65536.0);
     p.seed = seed; p.seed_dev = seed_dev;
     const bool vec = H % 4 == 0 && aligned16(h) && aligned16(out) && aligned16(E);
-    return launch_diag<false>((hipStream_t)stream, p, dtype, vec);
+    return packed ? launch_diag<false, true>((hipStream_t)stream, p, dtype, vec) : launch_diag<false, false>((hipStream_t)stream, p, dtype, vec);
+}
+
+static int diag_bwd(void* stream, const void* dY, const void* Y, const void* h, int dtype, const float* E, const int64_t* deprel,
+                    const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label, const int32_t* rowT_ptr, const int32_t* colT_idx,
+                    const int32_t* n_live, bool packed, long long n_rows, int T, int nnz_cap, int H, void* dh, float* dE, float scale,
+                    const char* what) {
+    GCNPT_REQUIRE(dY && Y && h && E && deprel && row_ptr && col_idx && label && rowT_ptr && colT_idx && dh && dE && (!packed || n_live),
+                  "%s: null pointer", what);
+    GCNPT_REQUIRE(n_rows > 0 && T > 0 && H > 0 && dtype_ok(dtype) && (!packed || nnz_cap > 0), "%s: bad argument", what);
+    if (n_rows > 0x7fffffffLL / 2) return fail(GCNPT_E_UNSUPPORTED, "%s: too many rows", what);
+    DiagParams p{};
+    p.h = h; p.y = Y; p.dy = dY; p.E = E; p.deprel = deprel; p.row_ptr = row_ptr; p.col_idx = col_idx; p.label = label;
+    p.rowT_ptr = rowT_ptr; p.colT_idx = colT_idx; p.out = dh; p.dE = dE;
+    p.n_live = n_live; p.nnz_cap = nnz_cap;
+    p.N = (int)n_rows; p.T = T; p.H = H; p.scale = scale;
+    const bool vec = H % 4 == 0 && aligned16(h) && aligned16(Y) && aligned16(dY) && aligned16(dh) && aligned16(E);
+    return packed ? launch_diag<true, true>((hipStream_t)stream, p, dtype, vec) : launch_diag<true, false>((hipStream_t)stream, p, dtype, vec);
+}
+
+extern "C" int gcnpt_diag_layer_fwd(void* stream, const void* h, int dtype, const float* E, const int64_t* deprel,
+                                    const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label, int B, int T, int H,
+                                    void* out, float drop_p, uint64_t seed, const uint64_t* seed_dev) {
+    GCNPT_REQUIRE(B > 0 && T > 0, "diag_layer_fwd: bad argument");
+    return diag_fwd(stream, h, dtype, E, deprel, row_ptr, col_idx, label, nullptr, false, (long long)B * T, T, 0, H, out, drop_p, seed, seed_dev,
+                    "diag_layer_fwd");
+}
+
+extern "C" int gcnpt_diag_layer_fwd_packed(void* stream, const void* h, int dtype, const float* E, const int64_t* deprel,
+                                           const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label, const int32_t* n_live,
+                                           int n_rows, int nnz_cap, int H, void* out, float drop_p, uint64_t seed, const uint64_t* seed_dev) {
+    return diag_fwd(stream, h, dtype, E, deprel, row_ptr, col_idx, label, n_live, true, n_rows, 1, nnz_cap, H, out, drop_p, seed, seed_dev,
+                    "diag_layer_fwd_packed");
 }
 
 extern "C" int gcnpt_diag_layer_bwd(void* stream, const void* dY, const void* Y, const void* h, int dtype, const float* E,
                                     const int64_t* deprel, const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label,
                                     const int32_t* rowT_ptr, const int32_t* colT_idx, int B, int T, int H, void* dh, float* dE,
                                     float scale) {
-    GCNPT_REQUIRE(dY && Y && h && E && deprel && row_ptr && col_idx && label && rowT_ptr && colT_idx && dh && dE, "diag_layer_bwd: null pointer");
-    GCNPT_REQUIRE(B > 0 && T > 0 && H > 0 && dtype_ok(dtype), "diag_layer_bwd: bad argument");
-    if ((long long)B * T > 0x7fffffffLL / 2) return fail(GCNPT_E_UNSUPPORTED, "diag_layer_bwd: B*T too large");
-    DiagParams p{};
-    p.h = h; p.y = Y; p.dy = dY; p.E = E; p.deprel = deprel; p.row_ptr = row_ptr; p.col_idx = col_idx; p.label = label;
-    p.rowT_ptr = rowT_ptr; p.colT_idx = colT_idx; p.out = dh; p.dE = dE;
-    p.N = B * T; p.T = T; p.H = H; p.scale = scale;
-    const bool vec = H % 4 == 0 && aligned16(h) && aligned16(Y) && aligned16(dY) && aligned16(dh) && aligned16(E);
-    return launch_diag<true>((hipStream_t)stream, p, dtype, vec);
+    GCNPT_REQUIRE(B > 0 && T > 0, "diag_layer_bwd: bad argument");
+    return diag_bwd(stream, dY, Y, h, dtype, E, deprel, row_ptr, col_idx, label, rowT_ptr, colT_idx, nullptr, false, (long long)B * T, T, 0, H, dh, dE,
+                    scale, "diag_layer_bwd");
+}
+
+extern "C" int gcnpt_diag_layer_bwd_packed(void* stream, const void* dY, const void* Y, const void* h, int dtype, const float* E,
+                                           const int64_t* deprel, const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label,
+                                           const int32_t* rowT_ptr, const int32_t* colT_idx, const int32_t* n_live, int n_rows, int nnz_cap,
+                                           int H, void* dh, float* dE, float scale) {
+    return diag_bwd(stream, dY, Y, h, dtype, E, deprel, row_ptr, col_idx, label, rowT_ptr, colT_idx, n_live, true, n_rows, 1, nnz_cap, H, dh, dE, scale,
+                    "diag_layer_bwd_packed");
 }

@@ -194,6 +194,40 @@ template <typename T> struct dgio<T, 1> {    // any H / alignment: `n` = 1 when 
     static __device__ __forceinline__ void st(T* p, int n, const float (&v)[1]) { if (n) io<T>::store1(p, v[0]); }
 };
 
+// zero row of H columns, written by one wave (CPL = 4: H % 4 == 0)
+template <typename T, int CPL>
+__device__ __forceinline__ void zero_row(T* row, int H, int lane) {
+    float z[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) z[j] = 0.0f;
+    for (int c0 = lane * CPL; c0 < H; c0 += 64 * CPL) dgio<T, CPL>::st(row + c0, 1, z);
+}
+
+// Where row r of a labelled adjacency finds its CSR segment and its neighbours, in either layout (full_kernels.hip, diag_kernels.hip).
+// A column value c of the row's sentence names row col0 + c, whose own segment is row_ptr[rp0 + c .. rp0 + c + 1]; t is the column
+// value that names row r itself.  Padded: r = b*T + t, rp0 = b*(T+1), col0 = b*T.  Token-packed (include/gcnpt.h, gcnpt_pack_trees):
+// columns are rows already, so rp0 = col0 = 0 and t = r.  A packed batch may hold more rows than tokens; rows from *n_live =
+// cu_seqlens[B] on belong to no sentence and their row_ptr entries were never written: `live` is false, the caller reads no adjacency
+// for them and writes a zero row.
+struct RowAddr { int rp0, col0, t; bool live; };
+template <bool PACKED>
+__device__ __forceinline__ RowAddr row_addr(const int32_t* n_live, int r, int T) {
+    if (PACKED) return RowAddr{0, 0, r, r < *n_live};
+    const int b = r / T;
+    return RowAddr{b * (T + 1), b * T, r - b * T, true};
+}
+// segment [beg, end) of the row that column value c names.  Packed: clamped to the nnz_cap entries allocated, so that no index leaves
+// the buffers whatever row_ptr holds (the packer leaves it unusable when its status reports GCNPT_E_CAPACITY)
+template <bool PACKED>
+__device__ __forceinline__ void row_seg(const int32_t* row_ptr, const RowAddr& a, int c, int nnz_cap, int& beg, int& end) {
+    beg = row_ptr[a.rp0 + c];
+    end = row_ptr[a.rp0 + c + 1];
+    if (PACKED) {
+        beg = min(max(beg, 0), nnz_cap);
+        end = min(max(end, beg), nnz_cap);
+    }
+}
+
 // the tile's 32 rows of an LDS bf16 tile X (stride in elements) as a fragment image (include/gcnpt.h): row-contraction
 // operand of the weight gradient, 8 consecutive rows per lane, read transposed with ds_read_b64_tr_b16
 __device__ __forceinline__ void emit_frag_image(uint4* F, const bf16_t* X, int stride, int width, int wave, int n_waves, int lane, size_t nks, size_t blk) {

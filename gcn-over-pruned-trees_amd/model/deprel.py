@@ -10,19 +10,28 @@ from ..utils import constant
 
 class _FullAggFn(torch.autograd.Function):
     """Aggregation + self loop + /(deg+1) + ReLU + dropout of a full_deprel layer in one kernel (csrc/full_kernels.hip); reference
-    model/gcn.py:308-311, 331, 340-344, 362, 385, 390-393."""
+    model/gcn.py:308-311, 331, 340-344, 362, 385, 390-393.  `trees`: a PrunedTrees (rows [B*T, H]) or a PackedTrees (rows [N, H], pos
+    may be None = every packed row was traversed, keep flags per packed CSR slot; rows past sum(len) come out zero)."""
 
     @staticmethod
     def forward(ctx, yf, yr, self_term, trees, pos, keep_f, keep_r, M, drop_p, seed, seed_dev):
-        B, T = trees.B, trees.T
         H = yf.shape[1]
         P = _lib.ptr
         yf = yf.to(torch.float32).contiguous()
         yr = yr.to(torch.float32).contiguous() if yr is not None else None
         st = self_term.to(torch.float32).contiguous() if self_term is not None else None
-        out = torch.empty((B * T, H), dtype=torch.float32, device=yf.device)
-        _lib.check(_lib.lib().gcnpt_full_agg_fwd(_lib.stream(), P(yf), P(yr), P(st), P(pos), P(trees.row_ptr), P(trees.col_idx), P(trees.label),
-                                                 P(keep_f), P(keep_r), B, T, H, int(M), P(out), float(drop_p), int(seed), P(seed_dev)))
+        N = trees.N if trees.packed else trees.B * trees.T
+        if st is not None and tuple(st.shape) != (N, H):
+            raise ValueError("full_agg: self_term %s does not fit %d rows of width %d" % (tuple(st.shape), N, H))
+        out = torch.empty((N, H), dtype=torch.float32, device=yf.device)
+        if trees.packed:
+            _lib.check(_lib.lib().gcnpt_full_agg_fwd_packed(_lib.stream(), P(yf), P(yr), P(st), P(pos), P(trees.row_ptr), P(trees.col_idx),
+                                                            P(trees.label), P(keep_f), P(keep_r), trees.n_live_ptr(), trees.N, trees.nnz_cap, H,
+                                                            int(M), P(out), float(drop_p), int(seed), P(seed_dev)))
+        else:
+            _lib.check(_lib.lib().gcnpt_full_agg_fwd(_lib.stream(), P(yf), P(yr), P(st), P(pos), P(trees.row_ptr), P(trees.col_idx), P(trees.label),
+                                                     P(keep_f), P(keep_r), trees.B, trees.T, H, int(M), P(out), float(drop_p), int(seed),
+                                                     P(seed_dev)))
         ctx.save_for_backward(out, pos, keep_f, keep_r)
         ctx.trees, ctx.M, ctx.rows = trees, int(M), (yf.shape[0], yr is not None, st is not None)
         ctx.scale = 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0
@@ -32,15 +41,20 @@ class _FullAggFn(torch.autograd.Function):
     def backward(ctx, g):
         out, pos, keep_f, keep_r = ctx.saved_tensors
         trees = ctx.trees
-        B, T, H = trees.B, trees.T, out.shape[1]
+        H = out.shape[1]
         rows, has_r, has_self = ctx.rows
         P = _lib.ptr
         g = g.to(torch.float32).contiguous()
         dagg = torch.empty_like(out)
         dyf = torch.zeros((rows, H), dtype=torch.float32, device=out.device)
         dyr = torch.zeros((rows, H), dtype=torch.float32, device=out.device) if has_r else None
-        _lib.check(_lib.lib().gcnpt_full_agg_bwd(_lib.stream(), P(g), P(out), P(pos), P(trees.row_ptr), P(trees.col_idx), P(trees.label),
-                                                 P(keep_f), P(keep_r), B, T, H, ctx.M, ctx.scale, P(dagg), P(dyf), P(dyr)))
+        if trees.packed:
+            _lib.check(_lib.lib().gcnpt_full_agg_bwd_packed(_lib.stream(), P(g), P(out), P(pos), P(trees.row_ptr), P(trees.col_idx), P(trees.label),
+                                                            P(keep_f), P(keep_r), trees.n_live_ptr(), trees.N, trees.nnz_cap, H, ctx.M, ctx.scale,
+                                                            P(dagg), P(dyf), P(dyr)))
+        else:
+            _lib.check(_lib.lib().gcnpt_full_agg_bwd(_lib.stream(), P(g), P(out), P(pos), P(trees.row_ptr), P(trees.col_idx), P(trees.label),
+                                                     P(keep_f), P(keep_r), trees.B, trees.T, H, ctx.M, ctx.scale, P(dagg), P(dyf), P(dyr)))
         return dyf, dyr, (dagg if has_self else None), None, None, None, None, None, None, None, None
 
 
@@ -153,7 +167,8 @@ def _zero_pad_row(grad):
 
 
 class _DiagLayerFn(torch.autograd.Function):
-    """One diagonal_deprel layer (csrc/diag_kernels.hip): reference model/gcn.py:272-294 + 390-393."""
+    """One diagonal_deprel layer (csrc/diag_kernels.hip): reference model/gcn.py:272-294 + 390-393.  `trees`: a PrunedTrees (h [B,T,H],
+    deprel [B,T]) or a PackedTrees (h [N,H], deprel the packed [N] ids of PackedTrees.pack_ids; rows past sum(len) come out zero)."""
 
     @staticmethod
     def forward(ctx, h, emb, deprel, trees, drop_p, seed, seed_dev=None):
@@ -163,16 +178,25 @@ class _DiagLayerFn(torch.autograd.Function):
             raise ValueError("diagonal_deprel needs the adjacency values: build the trees with want_label=True")
         B, T = trees.B, trees.T
         H = h.shape[-1]
-        if h.shape[0] * h.shape[1] != B * T or emb.shape != (constant.N_DEPREL, H) or deprel.numel() != B * T:
-            raise ValueError("diag layer: h %s, table %s, deprel %s do not fit %d x %d trees" %
-                             (tuple(h.shape), tuple(emb.shape), tuple(deprel.shape), B, T))
+        N = trees.N if trees.packed else B * T
+        if h.numel() != N * H or emb.shape != (constant.N_DEPREL, H) or deprel.numel() != N:
+            raise ValueError("diag layer: h %s, table %s, deprel %s do not fit the trees' %d rows" %
+                             (tuple(h.shape), tuple(emb.shape), tuple(deprel.shape), N))
+        if trees.packed and trees.rowT_ptr is None and any(ctx.needs_input_grad[:2]):
+            raise ValueError("diagonal_deprel's backward needs the transposed pattern: build the packed trees with want_transpose=True")
         h = h.contiguous()
         E = emb.detach().float().contiguous()
         deprel = deprel.contiguous()
         out = torch.empty_like(h)
-        _lib.check(_lib.lib().gcnpt_diag_layer_fwd(_lib.stream(), _lib.ptr(h), _lib.dtype_code(h.dtype), _lib.ptr(E), _lib.ptr(deprel),
-                                                   _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx), _lib.ptr(trees.label), B, T, H,
-                                                   _lib.ptr(out), float(drop_p), int(seed), _lib.ptr(seed_dev)))
+        if trees.packed:
+            _lib.check(_lib.lib().gcnpt_diag_layer_fwd_packed(_lib.stream(), _lib.ptr(h), _lib.dtype_code(h.dtype), _lib.ptr(E), _lib.ptr(deprel),
+                                                              _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx), _lib.ptr(trees.label),
+                                                              trees.n_live_ptr(), trees.N, trees.nnz_cap, H, _lib.ptr(out), float(drop_p),
+                                                              int(seed), _lib.ptr(seed_dev)))
+        else:
+            _lib.check(_lib.lib().gcnpt_diag_layer_fwd(_lib.stream(), _lib.ptr(h), _lib.dtype_code(h.dtype), _lib.ptr(E), _lib.ptr(deprel),
+                                                       _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx), _lib.ptr(trees.label), B, T, H,
+                                                       _lib.ptr(out), float(drop_p), int(seed), _lib.ptr(seed_dev)))
         ctx.trees, ctx.scale = trees, (1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0)
         ctx.save_for_backward(h, out, E, deprel)
         return out
@@ -185,13 +209,17 @@ class _DiagLayerFn(torch.autograd.Function):
         gout = gout.to(h.dtype).contiguous()
         dh = torch.empty_like(h)
         dE = torch.zeros_like(E)
-        _lib.check(_lib.lib().gcnpt_diag_layer_bwd(_lib.stream(), _lib.ptr(gout), _lib.ptr(out), _lib.ptr(h), _lib.dtype_code(h.dtype),
-                                                   _lib.ptr(E), _lib.ptr(deprel), _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx),
-                                                   _lib.ptr(trees.label), _lib.ptr(trees.rowT_ptr), _lib.ptr(trees.colT_idx), B, T, H,
-                                                   _lib.ptr(dh), _lib.ptr(dE), ctx.scale))
+        args = (_lib.stream(), _lib.ptr(gout), _lib.ptr(out), _lib.ptr(h), _lib.dtype_code(h.dtype), _lib.ptr(E), _lib.ptr(deprel),
+                _lib.ptr(trees.row_ptr), _lib.ptr(trees.col_idx), _lib.ptr(trees.label), _lib.ptr(trees.rowT_ptr), _lib.ptr(trees.colT_idx))
+        if trees.packed:
+            _lib.check(_lib.lib().gcnpt_diag_layer_bwd_packed(*args, trees.n_live_ptr(), trees.N, trees.nnz_cap, H, _lib.ptr(dh), _lib.ptr(dE),
+                                                              ctx.scale))
+        else:
+            _lib.check(_lib.lib().gcnpt_diag_layer_bwd(*args, B, T, H, _lib.ptr(dh), _lib.ptr(dE), ctx.scale))
         return dh, dE, None, None, None, None, None
 
 
 def diag_layer(h, deprel_table, deprel, trees, drop_p=0.0, seed=0, seed_dev=None):
-    """dropout(relu(((F (E[deprel] * h)) + (R (E[deprel+42] * h)) + E[84] * h) / (deg + 1))) for h [B,T,H] (fp32 or bf16)."""
+    """dropout(relu(((F (E[deprel] * h)) + (R (E[deprel+42] * h)) + E[84] * h) / (deg + 1))) for h [B,T,H] (fp32 or bf16), or -- `trees` a
+    PackedTrees -- token-packed h [N,H] with packed `deprel` [N]."""
     return _DiagLayerFn.apply(h, deprel_table, deprel, trees, drop_p, seed, seed_dev)

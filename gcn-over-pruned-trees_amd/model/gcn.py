@@ -19,7 +19,9 @@ BiLSTM unless opt['gcn_native_rnn'] is set.
 New optional `opt` keys (defaults reproduce the reference): `gcn_dtype` = 'fp32' | 'bf16' (MFMA operand /
 activation storage type inside the layer stack), `gcn_check_trees` = True (synchronise once per forward to
 raise on malformed trees the way the reference does; False keeps the step free of host syncs), `gcn_packed` = False (True: the
-layer loop runs on token-packed rows, sum(len) instead of B*T, padding only at the module boundary), `gcn_graph_rng` = False
+layer loop runs on token-packed rows, sum(len) instead of B*T, padding only at the module boundary -- every adj_type: the relation-aware
+variants then take any labelled PackedTrees, TreeCache.batch_packed's included, traverse every packed row and never synchronise),
+`gcn_graph_rng` = False
 (True: dropout seeds that survive hipGraph capture), `gcn_pool_handover` = True (layer stack + poolings as one op whose backward
 hands the top layer its dZ), `gcn_pack_with_trees` = True (the tree launch also packs the weights in a training step),
 `gcn_sparse_emb_grad` = False (True: the word-embedding table's gradient is a row-sparse tensor of the batch's token rows, for
@@ -181,10 +183,12 @@ class GCNRelationModel(nn.Module):
             # lengths, head_to_tree, tree_to_adj and the upload (gcn.py:96-112) in one launch, no host round trip; in a training step the
             # same launch packs the layer weights on the CUs the tree build leaves idle (one launch boundary less)
             pack = self.gcn.weight_pack(head.shape[0], head.shape[1]) if self.opt.get('gcn_pack_with_trees', True) else None
-            if self.opt.get('gcn_packed', False) and self.adj_type == 'regular' and not self.opt.get('gcn_pooled_only', False):
+            if self.opt.get('gcn_packed', False) and not self.opt.get('gcn_pooled_only', False):
                 # token-packed rows: the layers run on sum(len) rows instead of B*T (one host sync for sum(len), where the reference syncs
-                # for the lengths anyway, gcn.py:96); the SAME launch writes the packed layout (and packs the weights)
-                trees = prune_to_csr_packed(head, subj_pos, obj_pos, deprel, self.opt['prune_k'], masks.eq(0).sum(1), masks=masks, pack=pack)
+                # for the lengths anyway, gcn.py:96); the SAME launch writes the packed layout (and packs the weights); the relation-aware
+                # variants read the adjacency values from it
+                trees = prune_to_csr_packed(head, subj_pos, obj_pos, deprel, self.opt['prune_k'], masks.eq(0).sum(1), masks=masks,
+                                            want_label=self.adj_type != 'regular', pack=pack)
                 if self.opt.get('gcn_check_trees', True):
                     trees.padded.check(expect_maxlen=head.shape[1])
                     trees.check()
@@ -311,11 +315,12 @@ class GCN(nn.Module):
 
     def _native_inputs(self, adj, words, pos, ner, use_rnn):
         """opt['gcn_native_embed']: what the lookups, the cat, _word_embeddings' dropout, in_drop and (PackedTrees, no LSTM) pack_rows
-        compute, from embed_inputs.  Returns (rows, whether they are token-packed).  float32, except that a bf16 module whose layer stack
-        reads them directly (no LSTM, regular adjacency) gets bfloat16.  Seeds as _dropout_plan's: the CPU generator per forward, or with
+        compute, from embed_inputs.  Returns (rows, whether they are token-packed: PackedTrees without an LSTM in front, on the regular path
+        or -- opt['gcn_packed'] -- a relation-aware one).  float32, except that a bf16 module whose layer stack reads them directly (no LSTM,
+        regular adjacency) gets bfloat16.  Seeds as _dropout_plan's: the CPU generator per forward, or with
         opt['gcn_graph_rng'] fixed base seeds plus the _rng_step device counter.  In eval() / without dropout the op is a pure gather."""
         direct = self.adj_type == 'regular' and not use_rnn
-        to_packed = direct and isinstance(adj, PackedTrees)
+        to_packed = not use_rnn and isinstance(adj, PackedTrees) and (direct or self._packed_deprel(adj))
         p_emb = self.emb_dropout if (self.training and words.dim() == 2) else 0.0
         p_in = self.in_drop.p if self.training else 0.0
         seeds, seed_dev = (0, 0), None
@@ -403,10 +408,36 @@ class GCN(nn.Module):
             return ps, [s if p > 0 else 0 for s, p in zip(self._base_seeds, ps)], self._rng_step
         return ps, [_draw_seed() if p > 0 else 0 for p in ps], None
 
-    def _forward_diagonal(self, adj, gcn_inputs, deprel):
+    def _packed_deprel(self, trees):
+        """Whether a relation-aware forward on these PackedTrees runs on the token-packed rows: opt['gcn_packed'] says so (without it the
+        variants keep to the padded adjacency a .pack()ed batch carries along).  Raises for packed trees that lack what the variant reads."""
+        if self.adj_type == 'regular' or not self.opt.get('gcn_packed', False):
+            return False
+        if trees.label is None:
+            raise ValueError("adj_type %r needs the adjacency values: build the packed trees with want_label=True" % self.adj_type)
+        if self.adj_type == 'diagonal_deprel' and trees.rowT_ptr is None and torch.is_grad_enabled():
+            raise ValueError("adj_type 'diagonal_deprel' needs the transposed pattern for its backward: build the packed trees with "
+                             "want_transpose=True")
+        return True
+
+    @staticmethod
+    def _packed_rows(trees, gcn_inputs, rows_packed):
+        """float32 [N, width] rows of a relation-aware forward on PackedTrees, the rows past sum(len) zero (the GEMMs around the kernels
+        run over all N rows, and what an allocation happens to hold must not reach a weight gradient): the padded inputs packed once, or
+        the rows embed_inputs packed already."""
+        if not rows_packed:
+            return trees.pack_rows(gcn_inputs.to(torch.float32), zero_tail=True)
+        x = gcn_inputs.to(torch.float32)
+        return torch.where(trees.live_rows().unsqueeze(1), x, x.new_zeros(()))
+
+    def _forward_diagonal(self, adj, gcn_inputs, deprel, rows_packed=False):
         """gcn.py:255-257, 272-294: Linear preprocessor (host BLAS), then the element-wise relation-scaled layers.
-        no_adj has no effect on this variant in the reference either (it only zeroes the matrix the regular path uses)."""
-        trees = adj if isinstance(adj, PrunedTrees) else adj_to_csr(adj, want_label=True)
+        no_adj has no effect on this variant in the reference either (it only zeroes the matrix the regular path uses).
+        On a PackedTrees (opt['gcn_packed']) the preprocessor and every layer see the N packed rows; the output is unpacked once."""
+        pk = adj if isinstance(adj, PackedTrees) else None
+        trees = adj if isinstance(adj, (PrunedTrees, PackedTrees)) else adj_to_csr(adj, want_label=True)
+        if pk is not None:
+            gcn_inputs, deprel = self._packed_rows(pk, gcn_inputs, rows_packed), pk.pack_ids(deprel)
         x = self.preprocessor(gcn_inputs).to(self.compute_dtype)
         table = self.deprel_emb.weight            # padding_idx=0: nn.Embedding's backward would zero row 0, the hook below does
         if table.requires_grad and not getattr(self, '_pad_hooked', False):
@@ -415,9 +446,11 @@ class GCN(nn.Module):
         ps, seeds, seed_dev = self._dropout_plan()
         for l in range(self.layers):
             x = diag_layer(x, table, deprel, trees, ps[l], seeds[l], seed_dev)
+        if pk is not None:
+            return pk.unpack_rows(x.float()), pk.padded.pool_mask
         return x.float(), trees.pool_mask
 
-    def _forward_full(self, adj, gcn_inputs, deprel, all_tokens=False):
+    def _forward_full(self, adj, gcn_inputs, deprel, all_tokens=False, rows_packed=False):
         """adj_type='full_deprel', gcn.py:296-388 + traverse_deprel / traverse_self_loop 400-434; the traversal's contraction runs on
         csrc/bilinear_kernels.hip in the module's precision: exact fp32 MFMA (default) or, with opt['gcn_dtype']='bf16', bf16 operands.
         trav(x, e)[n] = sum_d e[n,d] (x[n] W3[d] + b3[d]) is only needed for tokens that sit in a pruned tree, so those are
@@ -426,17 +459,25 @@ class GCN(nn.Module):
         contraction runs on the hand-written kernels in both precisions (a library GEMM only when Tin > 256).  Everything around it -- aggregation of the traversed rows over the forward / reverse entries of the
         device pruner's CSR (picked by label range), edge dropout, the self-loop term, /(deg+1), ReLU, dropout -- is ONE kernel
         (csrc/full_kernels.hip, gcnpt_full_agg_fwd / _bwd).  The reference materialises [B,T,D,Tin] for all tokens and multiplies
-        dense [B,T,T] matrices instead."""
+        dense [B,T,T] matrices instead.
+        On a PackedTrees (opt['gcn_packed']) the rows are the N token-packed ones: all of them are traversed (no compaction, no host sync,
+        whatever gcn_check_trees says -- fewer rows than B*T, more than the in-tree count), the self-loop GEMM sees N rows, the edge keep
+        flags are drawn per packed CSR slot, and the output is unpacked once, at the end."""
         opt = self.opt
-        trees = adj if isinstance(adj, PrunedTrees) else adj_to_csr(adj, want_label=True)
+        pk = adj if isinstance(adj, PackedTrees) else None
+        trees = adj if isinstance(adj, (PrunedTrees, PackedTrees)) else adj_to_csr(adj, want_label=True)
         if trees.label is None:
             raise ValueError("full_deprel needs the adjacency values: build the trees with want_label=True")
-        B, T, cap = trees.B, trees.T, trees.cap
-        N, D, H = B * T, opt['deprel_emb_dim'], self.mem_dim
+        B, T = trees.B, trees.T
+        N, n_slots = (pk.N, pk.nnz_cap) if pk is not None else (B * T, B * trees.cap)
+        D, H = opt['deprel_emb_dim'], self.mem_dim
         dev = trees.device
         max_depth = opt.get('deprel_max_depth', 2)
         directed, self_loop = bool(opt.get('deprel_directed', False)), bool(opt.get('deprel_self_loop', True))
-        if all_tokens or not opt.get('gcn_check_trees', True):
+        if pk is not None:
+            tok = pos = None                                             # identity: packed row r is row r of the traversal
+            gcn_inputs = self._packed_rows(pk, gcn_inputs, rows_packed)
+        elif all_tokens or not opt.get('gcn_check_trees', True):
             # no compaction, no sync: every row is traversed (CompactTrees: the rows ARE the tokens of the pruned trees)
             tok = torch.arange(N, device=dev)
             pos = tok.to(torch.int32)
@@ -444,8 +485,8 @@ class GCN(nn.Module):
             tok = torch.nonzero(~trees.pool_mask.view(-1)).squeeze(1)                            # tokens of the pruned trees
             pos = torch.full((N,), -1, dtype=torch.int32, device=dev)
             pos[tok] = torch.arange(tok.numel(), device=dev, dtype=torch.int32)
-        M = int(tok.numel())
-        deprel_tok = deprel.reshape(-1)[tok]
+        M = int(tok.numel()) if tok is not None else N
+        deprel_tok = deprel.reshape(-1)[tok] if tok is not None else pk.pack_ids(deprel)
         b3 = self.W.bias.reshape(D, H)                                                            # gcn.py:303
         x = gcn_inputs.to(torch.float32)
         ps, seeds, seed_dev = self._dropout_plan()
@@ -456,7 +497,7 @@ class GCN(nn.Module):
                                    % (l, Tin, self.W.weight.shape[1]))
             Wk = self.W.weight.reshape(D * Tin, H)                                                # W3[d,t,h] flattened over (d,t), gcn.py:301
             xf = x.reshape(N, Tin)
-            xt = xf[tok]
+            xt = xf[tok] if tok is not None else xf
             plain = l >= max_depth                                                                # gcn.py:323-324, 355-356, 371-374
             ys, keeps = [None, None], [None, None]
             for k, (shift, on) in enumerate(((0, True), (constant.DEPREL_FORWARD_BOUND, not directed))):
@@ -476,7 +517,7 @@ class GCN(nn.Module):
                     ys[k] = torch.mm((e.unsqueeze(2) * xt.unsqueeze(1)).reshape(-1, D * Tin), Wk) + torch.mm(e, b3)
                 edge_keep = opt.get('edge_keep_prob', 1.0)
                 if self.training and edge_keep < 1.0:                                             # maybe_drop_edges, gcn.py:436-449
-                    keeps[k] = torch.empty((B * cap,), device=dev).bernoulli_(edge_keep).to(torch.uint8)
+                    keeps[k] = torch.empty((n_slots,), device=dev).bernoulli_(edge_keep).to(torch.uint8)
             self_term = None
             if self_loop:                                                                         # gcn.py:366-385, 417-434 (plain GEMMs)
                 se = torch.ones((D,), device=dev) if plain else self.deprel_emb.weight[constant.SELF_LOOP_INDEX]
@@ -484,7 +525,9 @@ class GCN(nn.Module):
             if ys[0] is None:
                 ys[0] = torch.zeros((1, H), dtype=torch.float32, device=dev)                      # no token sits in a tree
             x = _FullAggFn.apply(ys[0], ys[1], self_term, trees, pos, keeps[0], keeps[1], M if M > 0 else 0, ps[l], seeds[l], seed_dev)
-            x = x.view(B, T, H)
+            x = x.view(B, T, H) if pk is None else x
+        if pk is not None:
+            return pk.unpack_rows(x), pk.padded.pool_mask
         return x, trees.pool_mask
 
     def forward(self, adj, inputs):
@@ -521,15 +564,15 @@ class GCN(nn.Module):
             gcn_inputs = embs
 
         packed = adj if isinstance(adj, PackedTrees) else None
-        if packed is not None and self.adj_type != 'regular':
+        if packed is not None and self.adj_type != 'regular' and not self._packed_deprel(packed):
             if not isinstance(packed.padded, PrunedTrees):
                 raise ValueError("adj_type %r runs on the padded adjacency, which trees pruned straight into the packed layout "
                                  "(prune_to_csr_packed, TreeCache.batch_packed) do not keep: use prune_to_csr(...).pack(...)" % self.adj_type)
             adj = packed.padded                                  # the deprel variants run on the padded layout
         if self.adj_type == 'diagonal_deprel':
-            return self._forward_diagonal(adj, gcn_inputs, deprel)
+            return self._forward_diagonal(adj, gcn_inputs, deprel, rows_packed)
         if self.adj_type == 'full_deprel':
-            return self._forward_full(adj, gcn_inputs, deprel, all_tokens=ct is not None)
+            return self._forward_full(adj, gcn_inputs, deprel, all_tokens=ct is not None, rows_packed=rows_packed)
         trees = adj if isinstance(adj, (PrunedTrees, PackedTrees)) else adj_to_csr(adj, want_label=False)   # gcn.py:260-262
         return self._forward_regular(trees, gcn_inputs, rows_packed)
 

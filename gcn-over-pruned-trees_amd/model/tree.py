@@ -167,7 +167,7 @@ class PackedTrees(object):
         self.cu_seqlens, self.row_ptr, self.col_idx, self.label = cu_seqlens, row_ptr, col_idx, label
         self.rowT_ptr, self.colT_idx, self.ell, self.ellT = rowT_ptr, colT_idx, ell, ellT
         self.pool_mask, self.row_sent, self.status = pool_mask, row_sent, status
-        self._empty = None
+        self._empty = self._live = None
 
     @property
     def device(self):
@@ -195,16 +195,36 @@ class PackedTrees(object):
         return (P(self.cu_seqlens), P(self.row_ptr), P(self.col_idx), P(self.label), P(self.rowT_ptr), P(self.colT_idx), P(self.ell),
                 P(self.ellT), P(self.pool_mask), P(self.row_sent), self.N, self.nnz_cap, P(self.status))
 
-    def pack_rows(self, t):
-        """[B,T,W] (or [B,T]) -> packed [N,W] ([N]); differentiable."""
-        return _PackRowsFn.apply(t, self)
+    def n_live_ptr(self):
+        """Device address of cu_seqlens[B] = sum(len): the `n_live` word of the C-ABI's packed deprel forms (rows from there on are dead)."""
+        return self.cu_seqlens.data_ptr() + 4 * self.B
+
+    def live_rows(self):
+        """bool [N]: the rows that hold a token (N, the rows allocated, may exceed sum(len)); no host sync."""
+        if self._live is None:
+            self._live = torch.arange(self.N, device=self.device, dtype=torch.int32) < self.cu_seqlens[self.B]
+        return self._live
+
+    def pack_rows(self, t, zero_tail=False):
+        """[B,T,W] (or [B,T]) -> packed [N,W] ([N]); differentiable.  Rows past sum(len) are left unwritten, or zero with zero_tail."""
+        return _PackRowsFn.apply(t, self, zero_tail)
+
+    def pack_ids(self, t, fill=0):
+        """int64 [B,T] ids (deprel, ...) -> packed int64 [N] (gcnpt_pack_ids); rows past sum(len) hold `fill`."""
+        _lib.require_gpu(t)
+        if t.dtype != torch.int64 or tuple(t.shape) != (self.B, self.T):
+            raise TypeError("pack_ids: an int64 [%d,%d] tensor, got %s %s" % (self.B, self.T, t.dtype, tuple(t.shape)))
+        dst = torch.empty((self.N,), dtype=torch.int64, device=t.device)
+        _lib.check(_lib.lib().gcnpt_pack_ids(_lib.stream(), _lib.ptr(t.contiguous()), _lib.ptr(self.cu_seqlens), self.B, self.T, _lib.ptr(dst),
+                                             self.N, int(fill)))
+        return dst
 
     def unpack_rows(self, t):
         """packed [N,W] -> [B,T,W], zero in the slots past each sentence's end; differentiable."""
         return _UnpackRowsFn.apply(t, self)
 
 
-def _move_rows(t, trees, unpack):
+def _move_rows(t, trees, unpack, zero_tail=False):
     lib = _lib.lib()
     if unpack:
         W = t.shape[-1]
@@ -215,25 +235,25 @@ def _move_rows(t, trees, unpack):
         flat = t.dim() == 2
         src = (t.unsqueeze(-1) if flat else t).contiguous()
         W = src.shape[-1]
-        dst = torch.empty((trees.N, W), dtype=t.dtype, device=t.device)
+        dst = (torch.zeros if zero_tail else torch.empty)((trees.N, W), dtype=t.dtype, device=t.device)
         fn = lib.gcnpt_pack_rows
     if src.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("pack/unpack_rows: float32 or bfloat16 rows (integer fields: use PackedTrees.row_sent / cu_seqlens)")
+        raise TypeError("pack/unpack_rows: float32 or bfloat16 rows (integer id fields: use PackedTrees.pack_ids)")
     _lib.check(fn(_lib.stream(), _lib.ptr(src), _lib.dtype_code(src.dtype), _lib.ptr(trees.cu_seqlens), trees.B, trees.T, W, _lib.ptr(dst)))
     return dst
 
 
 class _PackRowsFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, t, trees):
+    def forward(ctx, t, trees, zero_tail=False):
         ctx.trees, ctx.flat = trees, t.dim() == 2
-        out = _move_rows(t, trees, unpack=False)
+        out = _move_rows(t, trees, unpack=False, zero_tail=zero_tail)
         return out.squeeze(-1) if ctx.flat else out
 
     @staticmethod
     def backward(ctx, g):
         g = _move_rows(g.unsqueeze(-1) if ctx.flat else g, ctx.trees, unpack=True)
-        return (g.squeeze(-1) if ctx.flat else g), None
+        return (g.squeeze(-1) if ctx.flat else g), None, None
 
 
 class _UnpackRowsFn(torch.autograd.Function):

@@ -355,6 +355,10 @@ int gcnpt_gather_trees_packed(void* stream, const int32_t* src_row_ptr, const in
                               const float* const* W, const int* H, const int* Din, int dtype, void* const* w_fwd, void* const* w_bwd);
 int gcnpt_pack_rows(void* stream, const void* src, int dtype, const int32_t* cu_seqlens, int B, int T, int W, void* dst);
 int gcnpt_unpack_rows(void* stream, const void* src, int dtype, const int32_t* cu_seqlens, int B, int T, int W, void* dst);
+/* gcnpt_pack_rows for the loader's id tensors (deprel, data/loader.py:117): src [dev] int64 [B*T] -> dst [dev] int64 [n_rows],
+ * dst[cu[b]+i] = src[b*T+i] for i < len[b]; the rows from cu_seqlens[B] to n_rows - 1, which belong to no sentence, get `fill` (an id the
+ * consumer's table holds), so dst is written completely.  No row outside [0, n_rows) is written whatever cu_seqlens holds. */
+int gcnpt_pack_ids(void* stream, const int64_t* src, const int32_t* cu_seqlens, int B, int T, int64_t* dst, int n_rows, int64_t fill);
 
 /* ---- the weight pack as a side job of the tree launch ---------------------------------------------------------------------
  * A training step needs the weights re-packed (gcnpt_pack_weights_multi) after every optimizer step and a batch's trees built
@@ -450,6 +454,21 @@ int gcnpt_diag_layer_bwd(void* stream, const void* dY, const void* Y, const void
                          const int64_t* deprel, const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label,
                          const int32_t* rowT_ptr, const int32_t* colT_idx, int B, int T, int H, void* dh, float* dE,
                          float scale);
+/* The same layer on TOKEN-PACKED rows (the arrays gcnpt_pack_trees / gcnpt_prune_to_csr_packed / gcnpt_gather_trees_packed write, with
+ * labels; the backward also needs the transposed pattern): h, out, Y, dY, dh are [n_rows,H], deprel [dev] int64 [n_rows] is PACKED
+ * (gcnpt_pack_ids), row_ptr / rowT_ptr have n_rows + 1 entries and the columns are packed rows.  n_live [dev] int32: the word
+ * cu_seqlens[B] (= sum(len)); n_rows may exceed it, and the rows from there on -- which belong to no sentence and whose row_ptr / rowT_ptr
+ * entries nobody wrote -- read no adjacency, get zero rows of out / dh and add nothing to dE (the contract of gcnpt_pool3_bwd_packed).
+ * nnz_cap = entries allocated: every offset read is clamped to it.  The dropout hash keys are the packed row and the column; the order of a
+ * row's entries and the arithmetic are the padded kernel's, so given the same operands a real token's forward row and dh row are
+ * bit-identical to the padded batch's. */
+int gcnpt_diag_layer_fwd_packed(void* stream, const void* h, int dtype, const float* E, const int64_t* deprel, const int32_t* row_ptr,
+                                const int32_t* col_idx, const int32_t* label, const int32_t* n_live, int n_rows, int nnz_cap, int H,
+                                void* out, float drop_p, uint64_t seed, const uint64_t* seed_dev);
+int gcnpt_diag_layer_bwd_packed(void* stream, const void* dY, const void* Y, const void* h, int dtype, const float* E,
+                                const int64_t* deprel, const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label,
+                                const int32_t* rowT_ptr, const int32_t* colT_idx, const int32_t* n_live, int n_rows, int nnz_cap, int H,
+                                void* dh, float* dE, float scale);
 
 /* ---- N4: loader-side pre-pruning (data/loader.py:81-141 builds batches from per-sentence features; trainer.py:52-73) ----
  * Pruning depends on the parse alone, so a dataset is pruned ONCE -- gcnpt_prune_to_csr over all S sentences padded to
@@ -538,6 +557,17 @@ int gcnpt_full_agg_fwd(void* stream, const float* yf, const float* yr, const flo
 int gcnpt_full_agg_bwd(void* stream, const float* dy, const float* y, const int32_t* pos, const int32_t* row_ptr, const int32_t* col_idx,
                        const int32_t* label, const uint8_t* keep_f, const uint8_t* keep_r, int B, int T, int H, int M, float scale,
                        float* dagg, float* dyf, float* dyr);
+/* The same on TOKEN-PACKED rows: out / self_term / dy / y / dagg are [n_rows,H], row_ptr has n_rows + 1 entries, the columns are packed rows,
+ * keep_f / keep_r hold one flag per packed CSR slot (nnz_cap of them).  pos [dev] int32 [n_rows] or NULL = identity (every packed row was
+ * traversed: M = n_rows).  n_live, the rows from cu_seqlens[B] on (zero rows of out and dagg, no adjacency read), nnz_cap, the dropout keys
+ * and bit-identity of a real token's forward row: as gcnpt_diag_layer_*_packed above. */
+int gcnpt_full_agg_fwd_packed(void* stream, const float* yf, const float* yr, const float* self_term, const int32_t* pos,
+                              const int32_t* row_ptr, const int32_t* col_idx, const int32_t* label, const uint8_t* keep_f,
+                              const uint8_t* keep_r, const int32_t* n_live, int n_rows, int nnz_cap, int H, int M, float* out, float drop_p,
+                              uint64_t seed, const uint64_t* seed_dev);
+int gcnpt_full_agg_bwd_packed(void* stream, const float* dy, const float* y, const int32_t* pos, const int32_t* row_ptr,
+                              const int32_t* col_idx, const int32_t* label, const uint8_t* keep_f, const uint8_t* keep_r,
+                              const int32_t* n_live, int n_rows, int nnz_cap, int H, int M, float scale, float* dagg, float* dyf, float* dyr);
 
 /* ---- the embedding front end, model/gcn.py:235-241 (+ EmbeddingDropout, model/dropouts.py:23-39): the layer stack's input in ONE launch ----
  *   out[row] = in_drop([emb_drop(emb[words]) | pos_emb[pos] | ner_emb[ner]]),  width Din = E0 + E1 + E2

@@ -13,6 +13,11 @@ weights; eager launches (ctypes + torch), one optimizer-free fwd+bwd per step.  
 --cells A,B: only the named cells (C2_gcn, C2_gcn_native_embed, C3_cgcn, ...); --no-copy: skip the copy bandwidth measurement
 --ab A,B [--repeats R]: A/B of two cells in ONE process: both models are built first, then R rounds (default 5) of 100 steps each,
       alternating A, B, A, B, ...; prints every round's ms per step with the median and the spread (max - min) per arm
+--adj-type full_deprel|diagonal_deprel [--repeats R]: the relation-aware model (no LSTM, hidden 200, deprel_emb_dim 50; full_deprel: a 200-wide
+      input, since its one shared weight serves every layer) in three arms built in ONE process -- `padded` (the default: gcn_check_trees
+      on, in-tree compaction with its host sync), `padded_nocheck` (gcn_check_trees=False: all B*T rows, no sync), `packed` (gcn_packed:
+      sum(len) rows, no sync; cached trees come from TreeCache.batch_packed with the host's row count) -- R rounds of 50 steps each,
+      alternating the arms; per arm the forward alone and the whole step (forward + backward), median and spread over the rounds
 """
 import argparse
 import json
@@ -35,8 +40,59 @@ def opt_for(rnn, dtype, native_rnn=False, native_embed=False, native_head=False)
                 gcn_dtype=dtype, gcn_check_trees=False, gcn_native_rnn=native_rnn, gcn_native_embed=native_embed, gcn_native_head=native_head)
 
 
+def deprel_arms(args, dev, inputs, labels, B, T):
+    """--adj-type: the three arms of a relation-aware model, alternating (see the module docstring)."""
+    full = args.adj_type == "full_deprel"
+    arms = (("padded", dict(gcn_check_trees=True)), ("padded_nocheck", dict()), ("packed", dict(gcn_packed=True)))
+    n_rows = int((inputs[1] == 0).sum().item())
+    idx = torch.arange(B, device=dev)
+    cache = tree.TreeCache.build(inputs[5], inputs[6], inputs[7], inputs[4], 1, masks=inputs[1], want_label=True)
+    out = dict(adj_type=args.adj_type, B=B, T=T, hidden=200, deprel_emb_dim=50, tokens=n_rows, steps_per_round=50, rounds=args.repeats)
+    for dtype in ("fp32", "bf16"):
+        models = {}
+        for name, kw in arms:
+            torch.manual_seed(1234)
+            opt = dict(opt_for(False, dtype), adj_type=args.adj_type, deprel_emb_dim=50, emb_dim=140 if full else 300, **kw)
+            models[name] = gcn.GCNClassifier(opt).to(dev).train()
+
+        def run(name, cached, backward):
+            model = models[name]
+            model.zero_grad(set_to_none=True)
+            trees = None
+            if cached:
+                trees = cache.batch_packed(idx, T, n_rows=n_rows) if name == "packed" else cache.batch(idx, T)
+            logits, pooled = model(inputs, trees=trees)
+            loss = model.loss(logits, pooled, labels)
+            if backward:
+                loss.backward()
+            return loss.detach()
+
+        def timed(name, cached, backward, n=50):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                run(name, cached, backward)
+            torch.cuda.synchronize()
+            return round((time.perf_counter() - t0) / n * 1e3, 3)
+
+        for cached in (False, True):
+            for name, _ in arms:
+                for _ in range(10):
+                    run(name, cached, True)
+            runs = {(name, part): [] for name, _ in arms for part in ("forward", "step")}
+            for _ in range(args.repeats):
+                for name, _ in arms:
+                    runs[(name, "forward")].append(timed(name, cached, False))
+                    runs[(name, "step")].append(timed(name, cached, True))
+            for (name, part), v in runs.items():
+                out["%s_%s_%s_%s" % (name, dtype, "cached_trees" if cached else "pruned_in_step", part)] = dict(
+                    ms=v, median=float(np.median(v)), spread=round(max(v) - min(v), 3))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--adj-type", default="regular", choices=("regular", "full_deprel", "diagonal_deprel"))
     ap.add_argument("--cells", default="")
     ap.add_argument("--no-copy", action="store_true")
     ap.add_argument("--ab", default="")
@@ -53,6 +109,9 @@ def main():
     inputs = (t(words), t(tb["masks"]), t(rng.randint(0, 47, size=(B, T)).astype(np.int64)), t(rng.randint(0, 15, size=(B, T)).astype(np.int64)),
               t(tb["deprel"]), t(tb["head"]), t(tb["subj_pos"]), t(tb["obj_pos"]))
     labels = t(rng.randint(0, 42, size=(B,)).astype(np.int64))
+    if args.adj_type != "regular":
+        deprel_arms(args, dev, inputs, labels, B, T)
+        return
     out = {}
     cells = (("C2_gcn", False, False, False, False), ("C2_gcn_native_embed", False, False, True, False), ("C2_gcn_native_head", False, False, False, True),
              ("C2_gcn_native_embed_native_head", False, False, True, True), ("C3_cgcn", True, False, False, False),
