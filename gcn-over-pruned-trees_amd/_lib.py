@@ -95,6 +95,7 @@ SIGNATURES = {
     "gcnpt_diag_layer_bwd_packed": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _f]),
     "gcnpt_gather_trees": (_i, [_p] * 11 + [_i, _i, _i, _p, _i, _i, _i] + [_p] * 9),
     "gcnpt_gather_trees_pack": (_i, [_p] * 11 + [_i, _i, _i, _p, _i, _i, _i] + [_p] * 9 + [_i, _p, _p, _p, _i, _p, _p]),
+    "gcnpt_gather_batch": (_i, [_p] * 10 + [_i, _i, _p, _i, _i] + [_p] * 11 + [ctypes.c_int64, _f, _u64, _p]),
     "gcnpt_compact_trees": (_i, [_p] * 10 + [_i] * 5 + [_p] * 11),
     "gcnpt_bilinear_packed_bytes": (_sz, [_i, _i, _i, _i]),
     "gcnpt_bilinear_supported": (_i, [_i, _i, _i, _i]),

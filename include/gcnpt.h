@@ -485,6 +485,30 @@ int gcnpt_gather_trees(void* stream, const int32_t* src_row_ptr, const int32_t* 
                        int32_t* row_ptr, int32_t* col_idx, int32_t* label, int32_t* rowT_ptr, int32_t* colT_idx,
                        int32_t* ell, int32_t* ellT, uint8_t* pool_mask, int32_t* status);
 
+/* N4, the loader tensors themselves: the dataset's token arrays stay in HBM as int32 [S*Ts] (src_*, padded to the dataset's longest
+ * sentence Ts; src_len / src_label int32 [S]; src_ner may be NULL -- SemEval has none), and ONE launch writes the tensors the model reads
+ * for the batch idx [dev] int64 [B] (data/loader.py:81-141).  It only enqueues: no workspace, no memset, every output element has exactly
+ * one writer, so it replays in a graph with nothing but idx (and *seed_dev) changing.  With s = idx[b], n = src_len[s]:
+ *   words, pos, ner, deprel, head, subj_pos, obj_pos  [dev] int64 [B*T] (ner NULL iff src_ner NULL): src_field[s*Ts+t] for t < n; behind it
+ *           0 (PAD_ID) in words / pos / ner / deprel / head and pos_fill in subj_pos / obj_pos (150 in loader.py:120-121; pooling on packed
+ *           rows relies on it being non-zero)
+ *   masks   [dev] uint8 [B*T] = (t >= n).  From the LENGTH; the reference derives it as words == 0 (loader.py:110), which is the same
+ *           on everything its loader produces
+ *   labels  [dev] int64 [B] = src_label[s];  lens [dev] int32 [B] = n (optional);  status [dev] int32 [B] (optional)
+ *   word dropout (loader.py:96-98, 182-186): a real token whose id is not UNK_ID (1) becomes UNK_ID when
+ *           !keep(hash(seed + (seed_dev ? *seed_dev : 0), b*T + t, 0), 0, thresh16) with the hash, keep rule and 16-bit threshold of p_word
+ *           that gcnpt_embed_fwd uses for p_emb: keyed on the batch SLOT, so a sentence held by two slots is dropped independently; p_word = 0
+ *           copies the ids as they are.  No other output depends on the seeds.
+ *   status[b] = 0, GCNPT_E_INVALID for idx[b] outside [0,S), GCNPT_E_LENGTH for n > T or n > Ts -- gcnpt_gather_trees' codes for the same
+ *           sentences; such a sentence is an empty row (all pad, lens[b] = 0, labels[b] = 0) and nothing outside the source arrays is read.
+ * Without a GPU: a missing required pointer, src_ner / ner not both given or both NULL, S, Ts, B or T < 1, p_word outside [0,1) or NaN
+ * -> GCNPT_E_INVALID before anything is enqueued; B*T >= 2^31 -> GCNPT_E_UNSUPPORTED. */
+int gcnpt_gather_batch(void* stream, const int32_t* src_words, const int32_t* src_pos, const int32_t* src_ner, const int32_t* src_deprel,
+                       const int32_t* src_head, const int32_t* src_subj_pos, const int32_t* src_obj_pos, const int32_t* src_len,
+                       const int32_t* src_label, int S, int Ts, const int64_t* idx, int B, int T, int64_t* words, uint8_t* masks,
+                       int64_t* pos, int64_t* ner, int64_t* deprel, int64_t* head, int64_t* subj_pos, int64_t* obj_pos, int64_t* labels,
+                       int32_t* lens, int32_t* status, int64_t pos_fill, float p_word, uint64_t seed, const uint64_t* seed_dev);
+
 /* ---- N1, second half: "pooled-only" rows (model/gcn.py:116-121 pools over the tokens of the pruned tree only; a tree token's
  * row of every layer depends on tree tokens only, the adjacency has no entry outside the tree, model/tree.py:167-204) ----
  * Rewrites the arrays of a [B, T] batch (src_*, as gcnpt_prune_to_csr / gcnpt_gather_trees / gcnpt_adj_to_csr wrote them) for a
