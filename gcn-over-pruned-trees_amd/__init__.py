@@ -12,6 +12,7 @@ Layout
   shard.py sentence sharding + flat-bucket gradient all-reduce for data parallel runs
   optim.py the single-process optimizer step: clip_grad_norm_ + SGD / MyAdagrad + zero_grad as one native call
   dataset.py the dataset's token arrays in HBM; a batch's loader tensors, word dropout included, in one launch
+  evaluate.py a split's predictions, loss and micro-F1 without a host sync: one scoring launch per batch, one read at the end
   utils/   restated constants and the synthetic TACRED-shaped batch generator
 
 Import as `gcn_over_pruned_trees_amd` (alias module at the repo root).

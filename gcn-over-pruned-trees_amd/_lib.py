@@ -115,6 +115,8 @@ SIGNATURES = {
     "gcnpt_head_linear_bwd": (_i, [_p, _p, _p, _p, _ll, _p, _p, _ll, _p, _p, _i, _i, _i, _i]),
     "gcnpt_head_loss_fwd": (_i, [_p, _p, _p, _p, _ll, _i, _f, _i, _i, _p, _p, _p, _p]),
     "gcnpt_head_loss_bwd": (_i, [_p, _p, _p, _p, _p, _ll, _i, _f, _i, _i, _p, _p]),
+    "gcnpt_eval_batch": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "gcnpt_eval_finish": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "gcnpt_optim_partials_floats": (_sz, [_i, _i]),
     "gcnpt_optim_step": (_i, [_p, _i, ctypes.POINTER(OptimTensor), _i, ctypes.POINTER(OptimTable), _i, _f, _f, _p, _i, _p]),
 }

@@ -15,7 +15,7 @@
 // where base and row stride allow -- into LDS, zero-filled outside the matrix, and the 16x16x4 operand layout (lane l: A[l & 15][k = l >> 4],
 // B[k = l >> 4][l & 15]) is read from there; the LDS row strides put the 64 lanes of such a read on 64 different banks.  Addresses are
 // clamped and values selected, so no load sits behind a bounds branch; only stores are guarded.
-#include "gcnpt_common.h"
+#include "head_common.h"
 
 namespace gcnpt {
 
@@ -188,26 +188,7 @@ __global__ __launch_bounds__(HD_THREADS) void head_linear_bwd_kernel(const float
 constexpr int HL_THREADS = 1024, HL_WAVES = HL_THREADS / WAVE;      // forward: ONE workgroup, a wave per row, rows w, w + 16, ...
 constexpr int HLB_THREADS = 256, HLB_WAVES = HLB_THREADS / WAVE;     // backward: a wave per row, 4 rows per workgroup
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {                 // butterfly: a fixed order, the same total in every lane
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
-// max and sum_c exp(z_c - max) of one row, by one wave
-__device__ __forceinline__ void row_softmax_stats(const float* __restrict__ z, int C, int lane, float& mx, float& den) {
-    float m = -INFINITY;
-    for (int c = lane; c < C; c += WAVE) m = fmaxf(m, z[c]);
-    mx = wave_max(m);
-    float s = 0.f;
-    for (int c = lane; c < C; c += WAVE) s += expf(z[c] - mx);
-    den = wave_sum(s);
-}
+// (wave_max, wave_sum, row_softmax_stats and row_argmax: head_common.h, shared with eval_kernels.hip)
 
 __global__ __launch_bounds__(HL_THREADS) void head_loss_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                                   const float* __restrict__ pooled, size_t ldp, int H, float l2, int M, int C,
@@ -227,12 +208,8 @@ __global__ __launch_bounds__(HL_THREADS) void head_loss_fwd_kernel(const float* 
             for (int c = lane; c < C; c += WAVE) probs[(size_t)m * C + c] = expf(z[c] - mx) * inv;
         }
         if (pred) {                                                   // the lowest index that holds the maximum
-            int best = 0x7fffffff;
-            for (int c = lane; c < C; c += WAVE)
-                if (z[c] == mx) best = min(best, c);
-#pragma unroll
-            for (int o = WAVE / 2; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, WAVE));
-            if (lane == 0) pred[m] = best < C ? best : 0;             // (an all-NaN row has no maximum: 0, as np.argmax gives)
+            const int best = row_argmax(z, C, lane, mx);
+            if (lane == 0) pred[m] = best;
         }
         if (labels) {
             const long long yl = labels[m];

@@ -658,6 +658,42 @@ int gcnpt_head_loss_fwd(void* stream, const float* logits, const int64_t* labels
 int gcnpt_head_loss_bwd(void* stream, const float* dloss, const float* logits, const int64_t* labels, const float* pooled, long long ldp, int H,
                         float l2, int M, int C, float* dlogits, float* dpooled);
 
+/* ---- evaluation of a whole split with no host round trip, model/trainer.py:112-124 + train.py:245-285 + utils/scorer.py:20-96: one
+ * gcnpt_eval_batch per batch scores its rows into accumulators indexed by SENTENCE NUMBER (so predictions come out in the dataset's order,
+ * no unsort), one gcnpt_eval_finish turns the accumulators into the loss and the micro-averaged scores; the host reads once, at the end.
+ * Counts take int32 integer atomics only (exact whatever the order); the one floating-point sum runs in a fixed order in the finishing
+ * launch: every result is bit-identical run to run.  C <= 1024 (the confusion matrix is C*C int32).
+ * The caller owns the buffers and their INITIAL VALUES: confusion [C,C], seen [S] and status [1] start at 0, pred [S] at -1; probs [S,C]
+ * and row_loss [S] need none (rows of sentences that were never scored keep what they held).
+ * gcnpt_eval_batch:  logits [dev] float32 [M,C]; labels [dev] int64 [M]; idx [dev] int64 [M], the sentence number of each row;
+ *   slot_status [dev] int32 [M] or NULL (gcnpt_gather_batch's status).  A row whose slot_status is non-zero or whose idx lies outside [0,S)
+ *   is skipped entirely -- nothing is read or written for it (the padded tail of a fixed-size last batch).  For every other row, s = idx[m]:
+ *     pred[s]       int64 = argmax of the row, the lowest index on ties (0 for an all-NaN row)
+ *     probs[s,:]    float32 = softmax of the row (max-subtracted); probs NULL = not wanted
+ *     row_loss[s]   float32 = (max - z[y]) + logf(sum_c exp(z_c - max)),  y = labels[m]
+ *     seen[s] += 1,  confusion[y, pred[s]] += 1
+ *   pred, probs and the per-row loss are gcnpt_head_loss_fwd's for the same row, bit for bit.  A label outside [0,C): bit 0 of status[0]
+ *   is set (atomic OR; status may be NULL), pred and probs are still written, row_loss[s] = 0, and neither seen nor confusion counts the row.
+ *   A sentence scored twice counts twice in confusion (as the reference's loop would count it) and keeps one of the two pred / row_loss.
+ *   no_relation is only validated here (both calls validate the same tuple).
+ * gcnpt_eval_finish:  one workgroup.
+ *     by_relation int32 [3,C] = correct (diagonal of confusion), guessed (column sums), gold (row sums) per class, the entry of class
+ *                 no_relation forced to 0 in all three (scorer.py:30-40); no_relation = -1: no class is excluded
+ *     totals      int32 [6] = rows scored (sum of confusion), distinct sentences scored (#{seen > 0}), sum correct, sum guessed, sum gold,
+ *                 sentences never seen
+ *     metrics     float64 [4] = loss, precision, recall, F1.  loss = mean of row_loss[s] over the sentences with seen[s] > 0 (0 when there
+ *                 is none), in double: thread t of 1024 sums sentences t, t + 1024, ... in order, then the partials are summed 32 at a time
+ *                 in thread order and the 32 sums in order.  p = guessed > 0 ? correct / guessed : 1;  r = gold > 0 ? correct / gold : 0;
+ *                 f = p + r > 0 ? 2 * p * r / (p + r) : 0, in double, left to right (scorer.py:84-92: the reference's floats bit for bit)
+ * Without a GPU: a NULL logits / labels / idx / pred / row_loss / seen / confusion (eval_batch) or confusion / seen / row_loss /
+ * by_relation / totals / metrics (eval_finish), M, C or S < 1, no_relation outside [-1,C) -> GCNPT_E_INVALID; C > 1024 ->
+ * GCNPT_E_UNSUPPORTED, before anything is enqueued. */
+int gcnpt_eval_batch(void* stream, const float* logits, const int64_t* labels, const int64_t* idx, const int32_t* slot_status, int M, int C,
+                     int S, int no_relation, int64_t* pred, float* probs, float* row_loss, int32_t* seen, int32_t* confusion,
+                     int32_t* status);
+int gcnpt_eval_finish(void* stream, const int32_t* confusion, const int32_t* seen, const float* row_loss, int C, int S, int no_relation,
+                      int32_t* by_relation, int32_t* totals, double* metrics);
+
 /* ---- the single-process optimizer step, reference train.py:225-227: clip_grad_norm_(parameters, max_grad_norm); optimizer.step();
  * optimizer.zero_grad() -- for torch.optim.SGD and for MyAdagrad (utils/torch_utils.py:10-90 with lr_decay = 0 and weight_decay = 0, the only
  * way the reference constructs it), on the parameters WHERE THEY LIVE: a list of dense tensors and a list of row-sparse tables.  Everything
